@@ -3,6 +3,8 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run; the ranks
                                                              talk through librccl bound with ctypes, sella_amd/comm.py)
+    python bench.py ... --dump-outputs DIR                  (also writes what the last timed step returned, rank 0's
+                                                             replica, as DIR/<name>.npy in float64: see dump_outputs)
 
 Metric (BASELINE.json): Davidson iterations per second on the synthetic 3N = 3072 Hessian of
 SURVEY.md §8(d).  One *step* = one complete `rayleigh_ritz(A, gamma=0.1, P, v0=g, 'jd0',
@@ -52,6 +54,28 @@ def hessian_like(n, seed, eps=5e-3):
     P = A + eps * 0.5 * (N + N.T)
     g = rng.normal(size=n)
     return A, P, g
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(directory, step_out):
+    """--dump-outputs: what one timed step returns to its caller — the Ritz values, the basis V and A V (n x k) and the
+    operator product count — as float64 .npy files, so that two builds can be compared output for output on identical
+    inputs.  Past DUMP_MAX_BYTES the same fixed, seeded sample of rows of V and A V is written (and the row indices)."""
+    lams, V, AV, nmv = step_out
+    n, k = V.shape
+    rows = None
+    room = (DUMP_MAX_BYTES - 8 * (len(lams) + 1) - 4096) // (8 * (2 * k + 1))
+    if n > room:
+        rows = np.sort(np.random.RandomState(0).choice(n, size=room, replace=False))
+        V, AV = V[rows], AV[rows]
+    os.makedirs(directory, exist_ok=True)
+    arrays = dict(lams=lams, V=V, AV=AV, nmatvec=np.array([nmv]))
+    if rows is not None:
+        arrays['rows'] = rows
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 class EnsembleMember:
@@ -166,7 +190,11 @@ def main():
     ap.add_argument('--block-n', type=int, default=12288, help='configs[4] leg: operator size (0 disables)')
     ap.add_argument('--block-iters', type=int, default=12)
     ap.add_argument('--block-eigh', type=int, default=1, help='time the full device eigh of the block operator at N = 1 (0: skip)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed step returned (rank 0's replica) as DIR/<name>.npy: lams, V, AV, nmatvec")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     rank = int(os.environ.get('RANK', '0'))
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -265,6 +293,8 @@ def main():
     ctx.sync()
     elapsed = time.perf_counter() - t0
     barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)        # `out`: the last timed step's result
 
     # Davidson loop alone (P's eigendecomposition kept from a previous optimizer phase).  Measured here, in the state the
     # timed loop above ran in: behind the threaded leg below every call of this process is ~0.16 ms slower for a while

@@ -110,6 +110,21 @@ def bench(out_path):
             f.write(buf.getvalue())
 
 
+def bench_dump(out_path, steps, dump_dir):
+    """bench.py in one process, the timed Davidson steps only, writing the last step's outputs to `dump_dir`."""
+    import io
+    from contextlib import redirect_stdout
+    import bench as bench_mod
+    sys.argv = ['bench.py', '--gpus', '1', '--steps', steps, '--warmup', '1', '--n', '36', '--option', 'eigh_tail_lds=0',
+                '--maxiter', '8', '--seeds', '2', '--starts', '1', '--converged-n', '0', '--no-cpu-baseline',
+                '--no-optimizer', '--concurrent', '0', '--block-n', '0', '--dump-outputs', dump_dir]
+    buf = io.StringIO()
+    with redirect_stdout(buf):
+        bench_mod.main()
+    with open(out_path, 'w') as f:
+        f.write(buf.getvalue())
+
+
 def panel(out_path):
     import torch.distributed as dist
     from sella_amd.parallel import RowShardedOperator
@@ -140,6 +155,8 @@ if __name__ == '__main__':
         ensemble_cohort(sys.argv[2], int(sys.argv[3]), sys.argv[1] == 'ensemble-cohort')
     elif sys.argv[1] == 'bench':
         bench(sys.argv[2])
+    elif sys.argv[1] == 'bench-dump':
+        bench_dump(sys.argv[2], sys.argv[3], sys.argv[4])
     elif sys.argv[1] == 'panel':
         panel(sys.argv[2])
     elif sys.argv[1] in ('ensemble-serial', 'ensemble-threads'):

@@ -116,6 +116,30 @@ def test_bench_two_ranks(tmp_path):
     assert ens['replicas'] == 4 and ens['per_gpu'] == 2 and ens['optimizer_steps_per_s'] > 0
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes what the last timed step returned; --steps sets which step that is.  Two problems
+    (--seeds 2 --starts 1) alternate: step 3 solves step 1's problem again, step 2 the other one."""
+    dumps = {}
+    for tag, steps in (('one', 1), ('one_again', 1), ('two', 2), ('three', 3)):
+        out, ddir = str(tmp_path / (tag + '.json')), str(tmp_path / tag)
+        launch(1, 'bench-dump', out, str(steps), ddir)
+        lines = [ln for ln in open(out).read().splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d['steps'] == steps and d['ms_per_step'] > 0
+        dumps[tag] = {f[:-4]: np.load(os.path.join(ddir, f)) for f in os.listdir(ddir)}
+    for a in dumps.values():
+        assert sorted(a) == ['AV', 'V', 'lams', 'nmatvec']
+        assert all(x.dtype == np.float64 for x in a.values())
+        k = a['V'].shape[1]
+        assert a['V'].shape == a['AV'].shape == (36, k) and a['lams'].shape == (k,) and k >= 1
+        np.testing.assert_allclose(a['V'].T @ a['V'], np.eye(k), atol=1e-12)
+    for name in dumps['one']:
+        np.testing.assert_array_equal(dumps['one'][name], dumps['one_again'][name])     # same arguments, same outputs
+        np.testing.assert_array_equal(dumps['one'][name], dumps['three'][name])
+    assert not np.array_equal(dumps['one']['lams'], dumps['two']['lams'])
+
+
 def test_row_sharded_block_product(tmp_path):
     """configs[4] exchange step: each rank multiplies its row panel, one all-gather assembles H V."""
     out = str(tmp_path / 'panel')
