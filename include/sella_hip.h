@@ -392,6 +392,39 @@ int sella_lr_materialize(sella_ctx* ctx, sella_mat B, sella_mat Wt, int r, const
 int sella_internals_eval(sella_ctx* ctx, int natoms, int nc, const double* pos, const double* tvec,
                          const double* tangent, double* q, double* grad, double* hvp, double* hess);
 
+/* ---- sparse internal-coordinate Jacobian / Hessians ------------------------------------------------- */
+/* SparseInternalJacobian, SparseInternalHessian(s) and SparseInternalHessiansSkeleton of sella/linalg.py:362-646.
+ * One object holds one topology — the skeleton of linalg.py:470-537: coordinate k touches the sizes[k] atoms
+ * atoms[sum_{k'<k} sizes[k'] ..] (0 <= sizes[k] <= natoms; an atom may repeat, a periodic image of itself, and its
+ * entries then accumulate) — plus device-resident values: gradient blocks (sizes[k], 3) and Hessian blocks
+ * (sizes[k], 3, sizes[k], 3), concatenated in coordinate order.
+ *   set_values / get_values: host <-> device copies of those buffers (NULL: that buffer is left alone);
+ *   eval: coordinates first .. first+count (all of natoms_per_coord = 2 / 3 / 4 atoms: bonds / angles / dihedrals)
+ *     filled from positions pos (count, natoms_per_coord, 3) and shift vectors tvec (count, natoms_per_coord-1, 3) or
+ *     NULL by the kernels of sella_internals_eval (gradient; Hessian too when `hessian`), without a trip to the host;
+ *   ldot(v): sum_k v_k H_k, (3 natoms x 3 natoms), linalg.py:601-618, summed in the reference's order (size groups in
+ *     order of first appearance, each group's sum from zero, coordinates and (a, b, i, j) in order inside it);
+ *   rdot(x): rows H_k x, (ncoords x 3 natoms), linalg.py:620-640;  ddot(u, x): u . H_k x (ncoords), :642-646;
+ *   hess_dense: the dense H_k of coordinates first .. first+count as (count 3 natoms x 3 natoms) rows, :420-442, 595-596;
+ *   jac_dense (count x 3 natoms) / jac_matvec (ncoords) / jac_rmatvec (3 natoms, add.at order): :377-401.
+ * `out` matrices are allocated by the caller with exactly the shapes above; every element, padding included, is
+ * stored.  Invalid shapes: SELLA_E_INVALID; a failed allocation: SELLA_E_NOMEM.                                    */
+typedef struct sella_sparse_int sella_sparse_int;
+int sella_sparse_int_create(sella_ctx* ctx, int natoms, int ncoords, const int* sizes, const int* atoms,
+                            sella_sparse_int** out);
+int sella_sparse_int_destroy(sella_sparse_int* s);
+int sella_sparse_int_set_values(sella_sparse_int* s, const double* grad_vals, const double* hess_vals);
+int sella_sparse_int_get_values(sella_sparse_int* s, double* grad_vals, double* hess_vals);
+int sella_sparse_int_eval(sella_sparse_int* s, int first, int count, int natoms_per_coord, const double* pos,
+                          const double* tvec, int hessian);
+int sella_sparse_int_ldot(sella_sparse_int* s, const double* v, sella_mat out);
+int sella_sparse_int_rdot(sella_sparse_int* s, const double* x, sella_mat out);
+int sella_sparse_int_ddot(sella_sparse_int* s, const double* u, const double* x, double* out);
+int sella_sparse_int_hess_dense(sella_sparse_int* s, int first, int count, sella_mat out);
+int sella_sparse_int_jac_dense(sella_sparse_int* s, int first, int count, sella_mat out);
+int sella_sparse_int_jac_matvec(sella_sparse_int* s, const double* x, double* out);
+int sella_sparse_int_jac_rmatvec(sella_sparse_int* s, const double* y, double* out);
+
 /* ---- EMT calculator (far side of the calculator boundary, sella/peswrapper.py:413-418) -------------- */
 /* Energy and gradient of the effective-medium potential (functional form of ase/calculators/emt.py).
  * pos (n x 3); par (9 x n): per-atom E0, s0, V0, eta2, kappa, lambda, n0, gamma1, gamma2 in eV / Angstrom;

@@ -148,6 +148,18 @@ SIGNATURES = {
                                       c_double_p, c_void_p, c_int_p]),
     'sella_internals_eval': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    'sella_sparse_int_create': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
+    'sella_sparse_int_destroy': (c_int, [c_void_p]),
+    'sella_sparse_int_set_values': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'sella_sparse_int_get_values': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'sella_sparse_int_eval': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
+    'sella_sparse_int_ldot': (c_int, [c_void_p, c_void_p, c_int]),
+    'sella_sparse_int_rdot': (c_int, [c_void_p, c_void_p, c_int]),
+    'sella_sparse_int_ddot': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'sella_sparse_int_hess_dense': (c_int, [c_void_p, c_int, c_int, c_int]),
+    'sella_sparse_int_jac_dense': (c_int, [c_void_p, c_int, c_int, c_int]),
+    'sella_sparse_int_jac_matvec': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'sella_sparse_int_jac_rmatvec': (c_int, [c_void_p, c_void_p, c_void_p]),
     'sella_emt_eval': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
                                c_double, c_double_p, c_void_p]),
     'sella_prof_enable': (c_int, [c_void_p, c_int]),

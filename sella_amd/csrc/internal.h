@@ -423,6 +423,11 @@ int eig_lowrank_update(sella_ctx* c, int n, double* w, Mat* V, Mat* Vt, const do
 // on the orthogonal complement of their span; *r_io and mu are updated (r grows by at most one per rank-one term)
 int lr_lowrank_update(sella_ctx* c, int n, int* r_io, double* mu, double lam0, Mat* Wt, const double* Up, const double* Zp,
                       int ldp, int kk, int* nrank1);
+// internals.hip: internals_kernel<natoms> queued over nc coordinates whose inputs are already on the device (dpos
+// (nc, natoms, 3), dtv (nc, natoms-1, 3) or null); q (nc) and grad (nc, 3 natoms) written, hess (nc, 3 natoms, 3 natoms)
+// too when not null.  No wait (sella_sparse_int_eval writes straight into the buffers of its topology).
+int internals_queue(sella_ctx* c, int natoms, int nc, const double* dpos, const double* dtv, double* dq, double* dgrad,
+                    double* dhess);
 // emt.hip: sella_emt_eval with the parameter table and shift vectors optionally resident (dconst: 9 n + 3 nshift doubles)
 int emt_eval_resident(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
                       const double* dconst, double rc, double acut, double cutoff, double beta, double* energy, double* grad);

@@ -178,6 +178,17 @@ int run_kind(sella_ctx* c, int nc, const double* dpos, const double* dtv, const 
 }
 
 }  // namespace
+
+int internals_queue(sella_ctx* c, int natoms, int nc, const double* dpos, const double* dtv, double* dq, double* dgrad,
+                    double* dhess) {
+    if (nc == 0) return SELLA_OK;
+    if (natoms == 2) return run_kind<2>(c, nc, dpos, dtv, nullptr, dq, dgrad, nullptr, dhess);
+    if (natoms == 3) return run_kind<3>(c, nc, dpos, dtv, nullptr, dq, dgrad, nullptr, dhess);
+    if (natoms == 4) return run_kind<4>(c, nc, dpos, dtv, nullptr, dq, dgrad, nullptr, dhess);
+    set_error("internals_queue: natoms must be 2, 3 or 4");
+    return SELLA_E_INVALID;
+}
+
 }  // namespace sella
 
 using namespace sella;

@@ -518,6 +518,11 @@ class Context:
                                               ptr(hvp), ptr(hess)))
         return q, grad, hvp, hess
 
+    def sparse_internals(self, natoms, sizes, atoms):
+        """A device-resident internal-coordinate topology (`DeviceSparseInternals`)."""
+        self._drain()
+        return DeviceSparseInternals(self, natoms, sizes, atoms)
+
     # ---- EMT calculator -------------------------------------------------------------------------
     def emt_eval(self, pos, par, shifts, rc, acut, cutoff, beta):
         """(energy, gradient (n, 3)) of the EMT potential; par (9, n), shifts (nshift, 3)."""
@@ -609,6 +614,102 @@ class DeviceFdOperator:
 
     Vs = property(lambda self: self._pairs()[0])
     AVs = property(lambda self: self._pairs()[1])
+
+
+class DeviceSparseInternals:
+    """One internal-coordinate topology on the device with its gradient and Hessian blocks (`sella_sparse_int_*`,
+    csrc/sparse_internal.hip): coordinate k touches atoms[sum(sizes[:k]) ..][:sizes[k]]; gradient blocks (sizes[k], 3)
+    and Hessian blocks (sizes[k], 3, sizes[k], 3) concatenated in coordinate order.  The contractions of
+    SparseInternalJacobian / SparseInternalHessians (sella/linalg.py:362-646) run on it; dense results come back as
+    `DeviceMatrix`es."""
+
+    def __init__(self, ctx, natoms, sizes, atoms):
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32).ravel()
+        atoms = np.ascontiguousarray(atoms, dtype=np.int32).ravel()
+        if atoms.size != int(sizes.astype(np.int64).sum()):
+            raise ValueError(f'{atoms.size} atom indices for coordinates of {int(sizes.sum())} atoms in all')
+        self.ctx, self.natoms, self.ncoords, self.ndof = ctx, int(natoms), len(sizes), 3 * int(natoms)
+        self.sizes = sizes
+        self.ngrad = 3 * atoms.size
+        self.nhess = int((9 * sizes.astype(np.int64) ** 2).sum())
+        h = c_void_p()
+        check(_lib.lib().sella_sparse_int_create(ctx._h, self.natoms, self.ncoords, ptr(sizes), ptr(atoms), byref(h)))
+        self._h = h
+        self._fin = ctx.child(weakref.finalize(self, _lib.lib().sella_sparse_int_destroy, h))
+
+    def set_values(self, grad=None, hess=None):
+        g = as_f64(grad).ravel() if grad is not None else None
+        H = as_f64(hess).ravel() if hess is not None else None
+        if (g is not None and g.size != self.ngrad) or (H is not None and H.size != self.nhess):
+            raise ValueError('gradient / Hessian values do not match the topology')
+        check(_lib.lib().sella_sparse_int_set_values(self._h, ptr(g), ptr(H)))
+
+    def get_values(self, grad=True, hess=True):
+        g = np.empty(self.ngrad) if grad else None
+        H = np.empty(self.nhess) if hess else None
+        check(_lib.lib().sella_sparse_int_get_values(self._h, ptr(g), ptr(H)))
+        return g, H
+
+    def eval(self, first, pos, tvec=None, hessian=True):
+        """Gradient (and Hessian) blocks of coordinates first .. first + len(pos) from their atom positions pos
+        (count, 2|3|4, 3) and shift vectors tvec (count, natoms - 1, 3), written on the device."""
+        pos = as_f64(pos)
+        tv = as_f64(tvec) if tvec is not None else None
+        check(_lib.lib().sella_sparse_int_eval(self._h, int(first), pos.shape[0], pos.shape[1], ptr(pos), ptr(tv),
+                                               int(bool(hessian))))
+
+    def _out(self, out, rows):
+        if out is None:
+            return self.ctx.zeros(rows, self.ndof)
+        if out.shape != (rows, self.ndof):
+            raise ValueError(f'out must be {(rows, self.ndof)}, got {out.shape}')
+        return out
+
+    def ldot(self, v, out=None):
+        v = as_f64(v, (self.ncoords,))
+        out = self._out(out, self.ndof)
+        check(_lib.lib().sella_sparse_int_ldot(self._h, ptr(v), out.handle))
+        return out
+
+    def rdot(self, x, out=None):
+        x = as_f64(x).ravel()
+        if x.size != self.ndof:
+            raise ValueError(f'x must have {self.ndof} entries')
+        out = self._out(out, self.ncoords)
+        check(_lib.lib().sella_sparse_int_rdot(self._h, ptr(x), out.handle))
+        return out
+
+    def ddot(self, u, x):
+        u, x = as_f64(u).ravel(), as_f64(x).ravel()
+        if u.size != self.ndof or x.size != self.ndof:
+            raise ValueError(f'u and x must have {self.ndof} entries')
+        w = np.zeros(self.ncoords)
+        check(_lib.lib().sella_sparse_int_ddot(self._h, ptr(u), ptr(x), ptr(w)))
+        return w
+
+    def hess_dense(self, first, count, out=None):
+        out = self._out(out, count * self.ndof)
+        check(_lib.lib().sella_sparse_int_hess_dense(self._h, int(first), int(count), out.handle))
+        return out
+
+    def jac_dense(self, first, count, out=None):
+        out = self._out(out, count)
+        check(_lib.lib().sella_sparse_int_jac_dense(self._h, int(first), int(count), out.handle))
+        return out
+
+    def jac_matvec(self, x):
+        x = as_f64(x).ravel()
+        if x.size != self.ndof:
+            raise ValueError(f'x must have {self.ndof} entries')
+        w = np.zeros(self.ncoords)
+        check(_lib.lib().sella_sparse_int_jac_matvec(self._h, ptr(x), ptr(w)))
+        return w
+
+    def jac_rmatvec(self, y):
+        y = as_f64(y, (self.ncoords,))
+        w = np.empty(self.ndof)
+        check(_lib.lib().sella_sparse_int_jac_rmatvec(self._h, ptr(y), ptr(w)))
+        return w
 
 
 class OptStep:

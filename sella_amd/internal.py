@@ -683,6 +683,48 @@ class InternalCoordinates:
         blocks.append((np.zeros((nrot, 0), dtype=np.int64), np.zeros((nrot, 0, 0))))
         return _HessianStack(self.ndof, blocks)
 
+    def _sparse_topology(self, kind, nrot):
+        """The device topology of bonds, angles, dihedrals and `nrot` empty rows, cached for as long as the index
+        arrays are unchanged (`SparseInternalHessiansSkeleton` for kind 'h', a Jacobian topology for 'g')."""
+        from .linalg import SparseInternalHessiansSkeleton, _SparseTopology
+        key = (len(self.atoms), nrot) + tuple(self.idx[k].tobytes() for k in self._order)
+        cache = self.__dict__.setdefault('_sparse_topo', {})
+        hit = cache.get(kind)
+        if hit is not None and hit[0] == key:
+            return hit[1]
+        indices = [ix for k in self._order for ix in self.idx[k]] + [np.zeros(0, dtype=np.int64)] * nrot
+        if kind == 'h':
+            topo = SparseInternalHessiansSkeleton._from_indices(len(self.atoms), indices)
+        else:
+            topo = _SparseTopology(len(self.atoms), indices)
+        cache[kind] = (key, topo)
+        return topo
+
+    def _sparse_fill(self, topo, hessian):
+        first = 0
+        for k in self._order:
+            pos, tvec, _ = self._batch(k)
+            if len(pos):
+                topo._dev.eval(first, pos, tvec, hessian=hessian)
+            first += len(pos)
+
+    def sparse_hessians(self):
+        """`hessian()` as `sella_amd.linalg.SparseInternalHessians` (same rows: bonds, angles, dihedrals, then the
+        empty rotation rows), the blocks evaluated on the device straight into its buffers (internal.py:2189-2305)."""
+        from .linalg import SparseInternalHessians
+        sk = self._sparse_topology('h', self.nrotations)
+        H = SparseInternalHessians._filled(sk, self.ndof)
+        self._sparse_fill(sk, hessian=True)
+        return H
+
+    def sparse_jacobian(self):
+        """`jacobian()` as `sella_amd.linalg.SparseInternalJacobian`, the gradient blocks evaluated on the device."""
+        from .linalg import SparseInternalJacobian
+        topo = self._sparse_topology('g', 0)
+        J = SparseInternalJacobian._filled(topo)
+        self._sparse_fill(topo, hessian=False)
+        return J
+
 
 def neighbour_bonds(atoms, rcut):
     """All pairs closer than rcut under the minimum-image convention of the periodic directions:

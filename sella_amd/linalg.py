@@ -1,4 +1,4 @@
-"""Operators of the hot path — drop-in for sella/linalg.py:14-353.
+"""Operators of the hot path — drop-in for sella/linalg.py:14-646.
 
   NumericalHessian   finite-difference Hessian-vector products through the calculator
                      boundary (linalg.py:14-101); the projection products U v / U^T Av run on
@@ -8,8 +8,12 @@
                      HBM (`_B_gpu`); its eigenvectors stay on the device both as columns and as
                      rows, ready for the Davidson preconditioner, the TS-BFGS |B| term and the
                      P-RFO step; numpy copies are produced lazily.
+  SparseInternalJacobian, SparseInternalHessian, SparseInternalHessiansSkeleton, SparseInternalHessians
+                     per-coordinate blocks of internal coordinates (linalg.py:362-646), topology and values resident
+                     on the device, contractions in csrc/sparse_internal.hip.
 """
 import os
+import weakref
 
 import numpy as np
 from scipy.sparse.linalg import LinearOperator
@@ -510,3 +514,256 @@ class ApproximateHessian(LinearOperator):
             tot = self.B + other
         return ApproximateHessian(self.dim, self.ncart, tot, self.update_method, self.symm,
                                   initialized=initialized)
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Sparse internal-coordinate Jacobian and Hessians (linalg.py:362-646).  The topology and the value blocks live on the
+# device (`DeviceSparseInternals`, csrc/sparse_internal.hip); the classes below keep the reference's constructors,
+# attributes and numpy-in / numpy-out semantics.
+# ------------------------------------------------------------------------------------------------------------------------
+_DENSE_SLAB_BYTES = 256 << 20          # device slab of the dense per-coordinate stack behind `asarray`
+
+
+class _SparseTopology:
+    """Atom lists of a set of coordinates on the device, and whose values its gradient ('g') and Hessian ('h') buffers
+    currently hold.  Several value sets may share one topology (a skeleton reused across steps): an object claims a
+    buffer before it computes with it, and the values of the previous holder are first brought to the host if they
+    exist nowhere else (device-filled values)."""
+
+    def __init__(self, natoms, indices):
+        self.natoms = int(natoms)
+        self.indices = [np.asarray(ix, dtype=np.int64).ravel() for ix in indices]
+        sizes = np.array([len(ix) for ix in self.indices], dtype=np.int64)
+        atoms = np.concatenate(self.indices) if self.indices else np.zeros(0, dtype=np.int64)
+        self._dev = get_context().sparse_internals(self.natoms, sizes, atoms)
+        self._holder = {}
+
+    def _current(self, kind):
+        ref = self._holder.get(kind)
+        return ref() if ref is not None else None
+
+    def claim(self, obj, kind):
+        """The buffer `kind` holds obj's values on return."""
+        cur = self._current(kind)
+        if cur is obj:
+            return self._dev
+        if cur is not None:
+            cur._spill(kind)
+        obj._upload(kind)
+        self._holder[kind] = weakref.ref(obj)
+        return self._dev
+
+    def overwrite(self, obj, kinds):
+        """obj is about to write the buffers `kinds` on the device itself (`DeviceSparseInternals.eval`)."""
+        for kind in kinds:
+            cur = self._current(kind)
+            if cur is not None and cur is not obj:
+                cur._spill(kind)
+            self._holder[kind] = weakref.ref(obj)
+        return self._dev
+
+
+class SparseInternalJacobian(LinearOperator):
+    """Wilson B-matrix of internal coordinates from per-coordinate gradient blocks (linalg.py:362-401): coordinate i
+    touches atoms `indices[i]` with gradient `vals[i]` (one 3-vector per atom; an atom listed twice accumulates).
+    `asarray`, `_matvec` and `_rmatvec` run on the device."""
+    dtype = np.float64
+
+    def __init__(self, natoms, indices, vals):
+        self.natoms = natoms
+        self.indices = indices
+        self._vals = vals
+        self.nints = len(indices)
+        super().__init__(self.dtype, (self.nints, 3 * natoms))
+        self._topo = None
+        self._gvals = None
+
+    @classmethod
+    def _filled(cls, topo):
+        """A Jacobian whose gradient blocks the device writes into `topo` (InternalCoordinates.sparse_jacobian)."""
+        self = cls.__new__(cls)
+        self.natoms, self.indices, self._vals, self.nints = topo.natoms, topo.indices, None, len(topo.indices)
+        LinearOperator.__init__(self, self.dtype, (self.nints, 3 * topo.natoms))
+        self._topo, self._gvals = topo, None
+        topo.overwrite(self, ('g',))
+        return self
+
+    @property
+    def vals(self):
+        if self._vals is None:
+            self._spill('g')
+            self._vals = np.split(self._gvals.reshape(-1, 3), np.cumsum([len(ix) for ix in self.indices])[:-1])
+        return self._vals
+
+    def _device(self):
+        if self._topo is None:
+            self._topo = _SparseTopology(self.natoms, self.indices)
+        return self._topo.claim(self, 'g')
+
+    def _upload(self, kind):
+        if self._gvals is None:
+            self._gvals = np.concatenate([np.asarray(v, dtype=np.float64).reshape(-1) for v in self._vals] or [np.zeros(0)])
+        self._topo._dev.set_values(grad=self._gvals)
+
+    def _spill(self, kind):
+        if self._gvals is None:
+            self._gvals = self._topo._dev.get_values(grad=True, hess=False)[0]
+
+    def asarray(self):
+        dev = self._device()
+        M = dev.jac_dense(0, self.nints)
+        out = M.numpy()
+        M.free()
+        return out
+
+    def _matvec(self, v):
+        return self._device().jac_matvec(np.asarray(v, dtype=np.float64).ravel())
+
+    def _rmatvec(self, v):
+        return self._device().jac_rmatvec(np.asarray(v, dtype=np.float64).ravel())
+
+
+class SparseInternalHessian(LinearOperator):
+    """Hessian of one internal coordinate (linalg.py:404-462): `vals` (m, 3, m, 3) on the m atoms `indices`, seen as a
+    (3 natoms, 3 natoms) operator.  Its products are at most 12 x 12 blocks and stay NumPy; the batched contractions
+    of many such blocks are `SparseInternalHessians`, on the device."""
+    dtype = np.float64
+
+    def __init__(self, natoms, indices, vals):
+        self.natoms = natoms
+        super().__init__(self.dtype, (3 * natoms, 3 * natoms))
+        self.indices = np.asarray(indices)
+        self.vals = np.asarray(vals)
+
+    def asarray(self):
+        n, m = self.natoms, len(self.indices)
+        H = np.zeros((n, 3, n, 3))
+        if m:
+            a, b = np.meshgrid(self.indices, self.indices, indexing='ij')
+            np.add.at(H, (a[:, :, None, None], np.arange(3)[None, None, :, None], b[:, :, None, None],
+                          np.arange(3)[None, None, None, :]), self.vals.transpose(0, 2, 1, 3))
+        return H.reshape(self.shape)
+
+    def _matvec(self, v):
+        x = np.asarray(v, dtype=np.float64).reshape(self.natoms, 3)
+        w = np.zeros_like(x)
+        if len(self.indices):
+            np.add.at(w, self.indices, np.einsum('aibj,bj->ai', self.vals, x[self.indices]))
+        return w.ravel()
+
+    def _rmatvec(self, v):
+        return self._matvec(v)
+
+
+class SparseInternalHessiansSkeleton(_SparseTopology):
+    """The index-only part of `SparseInternalHessians` (linalg.py:465-537): the atom lists of the coordinates, their
+    grouping by size and the inverted indices of the contractions, built once and kept on the device.  It depends on
+    neither positions nor values, so it is reused for as long as the set of coordinates is unchanged."""
+
+    def __init__(self, hessians, natoms):
+        super().__init__(natoms, [h.indices for h in hessians])
+        self.n_hess = len(hessians)
+
+    @classmethod
+    def _from_indices(cls, natoms, indices):
+        self = cls.__new__(cls)
+        _SparseTopology.__init__(self, natoms, indices)
+        self.n_hess = len(self.indices)
+        return self
+
+
+class SparseInternalHessians:
+    """The Hessians of a set of internal coordinates (linalg.py:540-646) with `ldot(v) = sum_i v_i H_i` (ndof, ndof),
+    `rdot(x)_i = H_i x` (n_hess, ndof), `ddot(u, x)_i = u . H_i x` and the dense stack `asarray()`.  The values are
+    packed and uploaded once; the contractions run on the device (csrc/sparse_internal.hip) — `ldot` in the reference's
+    summation order, bit for bit — and `ldot_dev` / `rdot_dev` leave their result there as a `DeviceMatrix`."""
+
+    def __init__(self, hessians, ndof, skeleton=None):
+        self._hessians = hessians
+        self.natoms = ndof // 3
+        self.shape = (len(hessians), ndof, ndof)
+        if skeleton is None:
+            skeleton = SparseInternalHessiansSkeleton(hessians, self.natoms)
+        elif skeleton.n_hess != len(hessians) or skeleton.natoms != self.natoms:
+            raise ValueError(
+                "skeleton was built for a different (n_hess, natoms); "
+                f"got skeleton ({skeleton.n_hess}, {skeleton.natoms}) vs "
+                f"this ({len(hessians)}, {self.natoms})"
+            )
+        self._skeleton = skeleton
+        vals = [np.asarray(h.vals, dtype=np.float64).reshape(-1) for h in hessians]
+        if [v.size for v in vals] != [9 * len(ix) ** 2 for ix in skeleton.indices]:
+            raise ValueError('Hessian blocks do not match the atom lists of the skeleton')
+        self._hvals = np.concatenate(vals) if vals else np.zeros(0)
+        skeleton.claim(self, 'h')
+
+    @classmethod
+    def _filled(cls, skeleton, ndof):
+        """Hessians whose blocks the device writes into `skeleton` (InternalCoordinates.sparse_hessians)."""
+        self = cls.__new__(cls)
+        self._hessians, self.natoms, self.shape = None, ndof // 3, (skeleton.n_hess, ndof, ndof)
+        self._skeleton, self._hvals = skeleton, None
+        skeleton.overwrite(self, ('g', 'h'))
+        return self
+
+    @property
+    def hessians(self):
+        if self._hessians is None:
+            self._spill('h')
+            sk, off = self._skeleton, 0
+            self._hessians = []
+            for ix in sk.indices:
+                m = len(ix)
+                self._hessians.append(SparseInternalHessian(self.natoms, ix, self._hvals[off:off + 9 * m * m]
+                                                            .reshape(m, 3, m, 3)))
+                off += 9 * m * m
+        return self._hessians
+
+    def _upload(self, kind):
+        self._skeleton._dev.set_values(hess=self._hvals)
+
+    def _spill(self, kind):
+        if kind == 'h' and self._hvals is None:
+            self._hvals = self._skeleton._dev.get_values(grad=False, hess=True)[1]
+
+    def _device(self):
+        return self._skeleton.claim(self, 'h')
+
+    def ldot_dev(self, v, out=None):
+        """sum_i v_i H_i as an (ndof, ndof) `DeviceMatrix` (written into `out` when given)."""
+        return self._device().ldot(np.asarray(v, dtype=np.float64).ravel(), out)
+
+    def rdot_dev(self, x, out=None):
+        """The rows H_i x as an (n_hess, ndof) `DeviceMatrix`."""
+        return self._device().rdot(np.asarray(x, dtype=np.float64).ravel(), out)
+
+    def ldot(self, v):
+        M = self.ldot_dev(v)
+        out = M.numpy()
+        M.free()
+        return out
+
+    def rdot(self, v):
+        M = self.rdot_dev(v)
+        out = M.numpy()
+        M.free()
+        return out
+
+    def ddot(self, u, v):
+        return self._device().ddot(np.asarray(u, dtype=np.float64).ravel(), np.asarray(v, dtype=np.float64).ravel())
+
+    def asarray(self):
+        n, ndof = self.shape[0], self.shape[1]
+        out = np.zeros(self.shape)
+        dev = self._device()
+        step = max(1, _DENSE_SLAB_BYTES // (8 * ndof * ndof))
+        for first in range(0, n, step):
+            count = min(step, n - first)
+            M = dev.hess_dense(first, count)
+            out[first:first + count] = M.numpy().reshape(count, ndof, ndof)
+            M.free()
+        return out
+
+    def __array__(self, dtype=None, copy=None):
+        out = self.asarray()
+        return out if dtype is None else out.astype(dtype, copy=False)
