@@ -392,6 +392,23 @@ int sella_lr_materialize(sella_ctx* ctx, sella_mat B, sella_mat Wt, int r, const
 int sella_internals_eval(sella_ctx* ctx, int natoms, int nc, const double* pos, const double* tvec,
                          const double* tangent, double* q, double* grad, double* hvp, double* hess);
 
+/* TRIC fragment rotations (sella/internal.py:1030-1078 `Rotation.calc` / `calc_gradient` / `calc_hessian`, closed forms
+ * :507-1010): the exponential map v_k = 2 c_{k+1} asinc(c_0), k = 0, 1, 2, of the quaternion c that best aligns each
+ * fragment's reference positions with its current ones (top eigenvector of the 4x4 matrix F(R), R = sum_i p_i (x) ref_i).
+ * Fragment f holds the atoms frag_atoms[frag_ptr[f] .. frag_ptr[f+1]) (at least one; indices in [0, natoms)).
+ *   pos (natoms, 3) positions; refpos (frag_ptr[nf], 3) reference positions, one row per CSR slot, centred per fragment;
+ *   q_prev (nf, 4) quaternion state, read and written: with flags bit 0 set (a value evaluation) c is q_prev projected
+ *     onto the top eigenspace of F (eigenvalues within 1e-10 of the largest), normalised, sign fixed so that c_0 >= 0
+ *     (the top eigenvector if the projection vanishes), and stored back; with the bit clear c = q_prev as given;
+ *   tangent (natoms, 3) or NULL.
+ * Outputs (host): val (nf, 3); grad (frag_ptr[nf] * 9): per fragment a (3 axes, m, 3) block at offset 9 frag_ptr[f];
+ * hvp the same layout (when tangent is given); hess, when not NULL, per fragment (3 axes, 3m, 3m) blocks one after the
+ * other (offset sum over earlier fragments of 27 m^2).  Derivatives use the pseudo-inverse of F - lam that drops gaps
+ * <= 1e-14, so diatomic and linear fragments give finite numbers.                                                      */
+int sella_internals_tric_eval(sella_ctx* ctx, int natoms, int nf, const int* frag_ptr, const int* frag_atoms,
+                              const double* pos, const double* refpos, double* q_prev, const double* tangent, int flags,
+                              double* val, double* grad, double* hvp, double* hess);
+
 /* ---- sparse internal-coordinate Jacobian / Hessians ------------------------------------------------- */
 /* SparseInternalJacobian, SparseInternalHessian(s) and SparseInternalHessiansSkeleton of sella/linalg.py:362-646.
  * One object holds one topology — the skeleton of linalg.py:470-537: coordinate k touches the sizes[k] atoms

@@ -148,6 +148,8 @@ SIGNATURES = {
                                       c_double_p, c_void_p, c_int_p]),
     'sella_internals_eval': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
+    'sella_internals_tric_eval': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     'sella_sparse_int_create': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
     'sella_sparse_int_destroy': (c_int, [c_void_p]),
     'sella_sparse_int_set_values': (c_int, [c_void_p, c_void_p, c_void_p]),

@@ -518,6 +518,32 @@ class Context:
                                               ptr(hvp), ptr(hess)))
         return q, grad, hvp, hess
 
+    def tric_eval(self, frag_ptr, frag_atoms, pos, refpos, q_prev, tangent=None, hessian=False, branch=True):
+        """TRIC rotations of fragments given as CSR (`sella_internals_tric_eval`, csrc/tric.hip): values (nf, 3);
+        gradient and H t (tangent (natoms, 3)) as flat arrays holding a (3, m, 3) block per fragment at 9 frag_ptr[f];
+        Hessian as a flat array of (3, 3m, 3m) blocks.  `q_prev` (nf, 4) is updated in place when `branch`."""
+        fp = np.ascontiguousarray(frag_ptr, dtype=np.int32).ravel()
+        fa = np.ascontiguousarray(frag_atoms, dtype=np.int32).ravel()
+        pos = as_f64(pos)
+        natoms = pos.shape[0]
+        nf = len(fp) - 1
+        ref = as_f64(refpos)
+        if ref.shape != (len(fa), 3) or fa.size != (fp[-1] if nf >= 0 else 0):
+            raise ValueError('refpos must be (len(frag_atoms), 3) and frag_ptr[-1] == len(frag_atoms)')
+        if not (isinstance(q_prev, np.ndarray) and q_prev.dtype == np.float64 and q_prev.flags.c_contiguous
+                and q_prev.shape == (nf, 4)):
+            raise ValueError('q_prev must be a C-contiguous float64 (nf, 4) array (it is updated in place)')
+        tan = as_f64(tangent, (natoms, 3)) if tangent is not None else None
+        val = np.empty((nf, 3))
+        grad = np.empty(9 * fa.size)
+        hvp = np.empty(9 * fa.size) if tan is not None else None
+        m = np.diff(fp).astype(np.int64)
+        hess = np.empty(int((27 * m * m).sum())) if hessian else None
+        check(_lib.lib().sella_internals_tric_eval(self._h, natoms, nf, ptr(fp), ptr(fa), ptr(pos), ptr(ref),
+                                                   ptr(q_prev), ptr(tan), int(bool(branch)), ptr(val), ptr(grad),
+                                                   ptr(hvp), ptr(hess)))
+        return val, grad, hvp, hess
+
     def sparse_internals(self, natoms, sizes, atoms):
         """A device-resident internal-coordinate topology (`DeviceSparseInternals`)."""
         self._drain()

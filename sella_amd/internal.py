@@ -10,8 +10,10 @@ sella/internal.py the saddle-point path needs:
 
 The reference differentiates these functions with JAX (CPU).  Here the derivatives are exact
 too: second-order forward-mode (hyper-dual) arithmetic inside one HIP kernel per coordinate kind
-(csrc/internals.hip), one thread per (coordinate, component) — no JAX.  Out of scope here: TRIC rotations,
-cell derivatives, dummy atoms, automatic topology search.
+(csrc/internals.hip), one thread per (coordinate, component) — no JAX.  TRIC fragment coordinates (translations of a
+fragment's centroid, rotations as the exponential map of its best-aligning quaternion, internal.py:1030-1078) are part of
+`InternalCoordinates`; the rotations are evaluated in closed form by csrc/tric.hip.  Out of scope here:
+cell derivatives, dummy atoms.
 """
 from functools import partialmethod
 
@@ -564,13 +566,17 @@ class Constraints:
 # sella/internal.py:1362-1902, 2189-2587: calc / jacobian / hessian ldot / hessian_rdot / wrap)
 # ------------------------------------------------------------------------------------------
 class InternalCoordinates:
-    """Bonds, angles and dihedrals of one structure as index arrays, evaluated in batches on the device.
+    """Bonds, angles and dihedrals of one structure as index arrays, evaluated in batches on the device, plus the TRIC
+    fragment coordinates (internal.py:3085-3144): translations and rotations.
 
     The reference keeps a Python object per coordinate and builds padded batch arrays from them
     (`_build_batched_arrays`, internal.py:1362-1529); here the index arrays ARE the representation:
     `bonds (nb, 2)`, `angles (na, 3)`, `dihedrals (nd, 4)` atom indices plus integer cell offsets
-    `*_ncvecs (n, natoms-1, 3)` for periodic images.  Order of the coordinates: bonds, angles, dihedrals.
-    Automatic topology search, dummy atoms and TRIC rotations are not part of this class.
+    `*_ncvecs (n, natoms-1, 3)` for periodic images.  Translations are `trans` [(atom indices, dim)] (the mean
+    position along one axis: linear, rows of weight 1/m, no curvature); rotations are `rot` [(fragment, axis)] over
+    the fragments `frags` (atom indices) with their centred reference positions `frag_ref` and quaternion state
+    `frag_q (nfrag, 4)` (csrc/tric.hip).  Order of the coordinates, the reference's: translations, bonds, angles,
+    dihedrals, rotations.  Dummy atoms are not part of this class.
     """
     _order = ('bonds', 'angles', 'dihedrals')
 
@@ -584,9 +590,84 @@ class InternalCoordinates:
             a = np.zeros((0, na), dtype=np.int64) if arr is None else np.asarray(arr, dtype=np.int64).reshape(-1, na)
             v = np.zeros((len(a), na - 1, 3)) if ncv is None else np.asarray(ncv, dtype=np.float64).reshape(len(a), na - 1, 3)
             self.idx[name], self.ncv[name] = a, v
+        self.trans = []                       # [(atom indices, dim)]
+        self.frags, self.frag_ref = [], []    # rotation fragments: atom indices, centred reference positions
+        self.frag_q = np.zeros((0, 4))        # quaternion state per fragment (read and written by every evaluation)
+        self.rot = []                         # [(fragment, axis)]
+        self.allow_fragments = False          # guess_hessian: 0.05 Hartree for the fragment coordinates, as the reference
 
     ndof = property(lambda self: 3 * len(self.atoms))
-    nint = property(lambda self: sum(len(self.idx[k]) for k in self._order))
+    nint = property(lambda self: sum(len(self.idx[k]) for k in self._order) + len(self.trans) + len(self.rot))
+
+    # ---- TRIC fragment coordinates (internal.py:3085-3144) -----------------------------------------------------
+    def add_translation(self, indices, dim=None):
+        """The centroid of `indices` (one atom index or several) along `dim`; all three axes when `dim` is None."""
+        ix = np.atleast_1d(np.asarray(indices, dtype=np.int64)).ravel()
+        if dim is None:
+            for d in range(3):
+                self.add_translation(ix, d)
+            return
+        for other, d in self.trans:
+            if d == dim and len(other) == len(ix) and set(other.tolist()) == set(ix.tolist()):
+                raise DuplicateInternalError(f'translation of {ix.tolist()} along {dim} exists')
+        self.trans.append((ix, int(dim)))
+
+    def add_rotation(self, indices, axis=None):
+        """The rotation of the fragment `indices` (two atoms or more) about `axis` away from its geometry now (its
+        reference), as the exponential map of the best-aligning quaternion; all three axes when `axis` is None."""
+        ix = np.asarray(indices, dtype=np.int64).ravel()
+        if len(ix) < 2:
+            raise ValueError('a rotation coordinate needs at least 2 atoms')
+        if axis is None:
+            for ax in range(3):
+                self.add_rotation(ix, ax)
+            return
+        frag = next((f for f, fx in enumerate(self.frags) if np.array_equal(fx, ix)), None)
+        if frag is None:
+            ref = np.array(self.atoms.positions[ix], dtype=np.float64)
+            self.frags.append(ix)
+            self.frag_ref.append(ref - ref.mean(axis=0))
+            self.frag_q = np.vstack([self.frag_q, [1.0, 0.0, 0.0, 0.0]])
+            frag = len(self.frags) - 1
+        if (frag, int(axis)) in self.rot:
+            raise DuplicateInternalError(f'rotation of {ix.tolist()} about {axis} exists')
+        self.rot.append((frag, int(axis)))
+
+    def _trans_rows(self):
+        """Translation rows as (dofs (k,), weights (k,)) per row."""
+        return [(3 * ix + d, np.full(len(ix), 1.0 / len(ix))) for ix, d in self.trans]
+
+    def _rot_eval(self, tangent=None, hessian=False):
+        """One device call for every fragment (csrc/tric.hip; updates `frag_q`): values (nrot,) and per rotation row
+        its dofs (3m,), gradient (3m,), H t (3m,) when `tangent` (3N,) is given, Hessian (3m, 3m) when `hessian`."""
+        if not self.rot:
+            return np.zeros(0), []
+        sizes = np.array([len(ix) for ix in self.frags], dtype=np.int64)
+        fp = np.concatenate([[0], np.cumsum(sizes)])
+        tan = None if tangent is None else np.asarray(tangent, dtype=np.float64).reshape(-1, 3)
+        val, g, hv, H = get_context().tric_eval(fp, np.concatenate(self.frags), self.atoms.positions,
+                                                np.concatenate(self.frag_ref), self.frag_q, tangent=tan,
+                                                hessian=hessian)
+        hoff = np.concatenate([[0], np.cumsum(27 * sizes * sizes)])
+        rows = []
+        for f, k in self.rot:
+            nv = 3 * sizes[f]
+            g0 = 9 * fp[f] + k * nv
+            h0 = hoff[f] + k * nv * nv
+            rows.append(((3 * self.frags[f][:, None] + np.arange(3)[None, :]).ravel(), g[g0:g0 + nv],
+                         None if hv is None else hv[g0:g0 + nv],
+                         H[h0:h0 + nv * nv].reshape(nv, nv) if hessian else None))
+        return np.array([val[f, k] for f, k in self.rot]), rows
+
+    @staticmethod
+    def _runs(rows, col):
+        """Consecutive rows of equal width stacked into blocks: [(dofs (n, w), rows[.][col] stacked)]."""
+        out, start = [], 0
+        for i in range(1, len(rows) + 1):
+            if i == len(rows) or len(rows[i][0]) != len(rows[start][0]):
+                out.append((np.stack([r[0] for r in rows[start:i]]), np.stack([r[col] for r in rows[start:i]])))
+                start = i
+        return out
 
     def _batch(self, name):
         idx = self.idx[name]
@@ -597,24 +678,34 @@ class InternalCoordinates:
 
     def calc(self):
         """q(x) (internal.py:1735-1778)."""
-        return np.concatenate([evaluate_kind(k, *self._batch(k)[:2], hessian=False)[0] for k in self._order])
+        x = self.atoms.positions.ravel()
+        tq = [np.array([w @ x[d] for d, w in self._trans_rows()])] if self.trans else []
+        rq = [self._rot_eval()[0]] if self.rot else []
+        return np.concatenate(tq + [evaluate_kind(k, *self._batch(k)[:2], hessian=False)[0] for k in self._order] + rq)
+
+    def _dihedral_slice(self):
+        lo = len(self.trans) + len(self.idx['bonds']) + len(self.idx['angles'])
+        return slice(lo, lo + len(self.idx['dihedrals']))
 
     def wrap(self, vec):
         """Map dihedral differences into (-pi, pi] (internal.py:2577-2587)."""
         nd = len(self.idx['dihedrals'])
         if nd:
             vec = np.array(vec, dtype=np.float64)
-            vec[-nd:] = (vec[-nd:] + np.pi) % (2 * np.pi) - np.pi
+            sl = self._dihedral_slice()
+            vec[sl] = (vec[sl] + np.pi) % (2 * np.pi) - np.pi
         return vec
 
     def jacobian_blocks(self):
         """The B-matrix as per-kind gradient blocks (`_JacobianStack`)."""
-        blocks = []
+        blocks = self._runs(self._trans_rows(), 1) if self.trans else []
         for k in self._order:
             pos, tvec, dofs = self._batch(k)
             nc = len(pos)
             g = evaluate_kind(k, pos, tvec, hessian=False)[1].reshape(nc, -1) if nc else np.zeros((0, dofs.shape[1]))
             blocks.append((dofs, g))
+        if self.rot:
+            blocks += self._runs(self._rot_eval()[1], 1)
         return _JacobianStack(self.ndof, blocks)
 
     def jacobian(self):
@@ -627,6 +718,13 @@ class InternalCoordinates:
         nint x 3N is ever dense on the way to the pseudo-inverse."""
         from scipy.sparse import csr_matrix
         data, cols, counts = [], [], []
+
+        def rows_of(rows):
+            for r in rows:
+                data.append(r[1])
+                cols.append(r[0])
+                counts.append(np.array([len(r[0])], dtype=np.int64))
+        rows_of(self._trans_rows())
         for k in self._order:
             pos, tvec, dofs = self._batch(k)
             nc = len(pos)
@@ -634,6 +732,8 @@ class InternalCoordinates:
                 data.append(evaluate_kind(k, pos, tvec, hessian=False)[1].reshape(-1))
                 cols.append(dofs.reshape(-1))
                 counts.append(np.full(nc, dofs.shape[1], dtype=np.int64))
+        if self.rot:
+            rows_of(self._rot_eval()[1])
         if not data:
             return csr_matrix((0, self.ndof))
         indptr = np.concatenate([[0], np.cumsum(np.concatenate(counts))])
@@ -644,7 +744,7 @@ class InternalCoordinates:
         v = np.asarray(v, dtype=np.float64).ravel()
         W = np.asarray(W, dtype=np.float64).reshape(self.ndof, -1)
         out = np.zeros((self.nint, W.shape[1]))
-        row = 0
+        row = len(self.trans)                               # translations are linear: zero rows
         for k in self._order:
             pos, tvec, dofs = self._batch(k)
             nc = len(pos)
@@ -653,13 +753,18 @@ class InternalCoordinates:
                 hv = evaluate_kind(k, pos, tvec, tangent=tan, hessian=False)[3].reshape(nc, -1)
                 out[row:row + nc] = np.einsum('ia,iak->ik', hv, W[dofs])
             row += nc
+        if self.rot:
+            for dofs, hv in self._runs(self._rot_eval(tangent=v)[1], 2):
+                out[row:row + len(dofs)] = np.einsum('ia,iak->ik', hv, W[dofs])
+                row += len(dofs)
         return out
 
     def hessian_rdot(self, v):
         """D(v)_i = H_i v as a dense (nint, 3N) matrix (internal.py:2307-2575: one HVP per coordinate, from the
         device's Hessian-vector kernel; the scatter is `_JacobianStack`'s)."""
         v = np.asarray(v, dtype=np.float64).ravel()
-        blocks = []
+        nt = len(self.trans)
+        blocks = [(np.zeros((nt, 0), dtype=np.int64), np.zeros((nt, 0)))]
         for k in self._order:
             pos, tvec, dofs = self._batch(k)
             nc = len(pos)
@@ -669,30 +774,36 @@ class InternalCoordinates:
             else:
                 hv = np.zeros((0, dofs.shape[1]))
             blocks.append((dofs, hv))
+        if self.rot:
+            blocks += self._runs(self._rot_eval(tangent=v)[1], 2)
         return _JacobianStack(self.ndof, blocks).asarray()
 
     def hessian(self):
         """Per-coordinate Hessian blocks with the `ldot` contraction (internal.py:2189-2305)."""
-        blocks = []
+        nt = len(self.trans)
+        blocks = [(np.zeros((nt, 0), dtype=np.int64), np.zeros((nt, 0, 0)))]     # translations: no curvature
         for k in self._order:
             pos, tvec, dofs = self._batch(k)
             nc, m = len(pos), 3 * _NATOMS[k]
             H = evaluate_kind(k, pos, tvec)[2].reshape(nc, m, m) if nc else np.zeros((0, m, m))
             blocks.append((dofs, H))
-        nrot = self.nrotations                              # linear in x at fixed generators: no curvature term
-        blocks.append((np.zeros((nrot, 0), dtype=np.int64), np.zeros((nrot, 0, 0))))
+        if self.rot:
+            blocks += self._runs(self._rot_eval(hessian=True)[1], 3)
         return _HessianStack(self.ndof, blocks)
 
-    def _sparse_topology(self, kind, nrot):
-        """The device topology of bonds, angles, dihedrals and `nrot` empty rows, cached for as long as the index
-        arrays are unchanged (`SparseInternalHessiansSkeleton` for kind 'h', a Jacobian topology for 'g')."""
+    def _sparse_topology(self, kind):
+        """The device topology of translations, bonds, angles, dihedrals and rotations, cached for as long as the
+        coordinate set is unchanged (`SparseInternalHessiansSkeleton` for kind 'h', a Jacobian topology for 'g')."""
         from .linalg import SparseInternalHessiansSkeleton, _SparseTopology
-        key = (len(self.atoms), nrot) + tuple(self.idx[k].tobytes() for k in self._order)
+        tix = [ix for ix, _ in self.trans]
+        rix = [self.frags[f] for f, _ in self.rot]
+        key = ((len(self.atoms),) + tuple(self.idx[k].tobytes() for k in self._order)
+               + (tuple(ix.tobytes() for ix in tix), tuple(ix.tobytes() for ix in rix)))
         cache = self.__dict__.setdefault('_sparse_topo', {})
         hit = cache.get(kind)
         if hit is not None and hit[0] == key:
             return hit[1]
-        indices = [ix for k in self._order for ix in self.idx[k]] + [np.zeros(0, dtype=np.int64)] * nrot
+        indices = tix + [ix for k in self._order for ix in self.idx[k]] + rix
         if kind == 'h':
             topo = SparseInternalHessiansSkeleton._from_indices(len(self.atoms), indices)
         else:
@@ -701,18 +812,38 @@ class InternalCoordinates:
         return topo
 
     def _sparse_fill(self, topo, hessian):
-        first = 0
+        first = len(self.trans)
         for k in self._order:
             pos, tvec, _ = self._batch(k)
             if len(pos):
                 topo._dev.eval(first, pos, tvec, hessian=hessian)
             first += len(pos)
+        if not (self.trans or self.rot):
+            return
+        # the fragment rows: translation weights and the rotation blocks of csrc/tric.hip, patched into the buffers
+        sizes = np.array([len(ix) for ix in topo.indices], dtype=np.int64)
+        goff = np.concatenate([[0], np.cumsum(3 * sizes)])
+        hoff = np.concatenate([[0], np.cumsum(9 * sizes * sizes)])
+        g, H = topo._dev.get_values(grad=True, hess=hessian)
+        for r, (ix, d) in enumerate(self.trans):
+            blk = np.zeros((len(ix), 3))
+            blk[:, d] = 1.0 / len(ix)
+            g[goff[r]:goff[r + 1]] = blk.ravel()
+            if hessian:
+                H[hoff[r]:hoff[r + 1]] = 0.0
+        if self.rot:
+            r0 = len(topo.indices) - len(self.rot)
+            for r, (_, gr, _, Hr) in enumerate(self._rot_eval(hessian=hessian)[1], start=r0):
+                g[goff[r]:goff[r + 1]] = gr
+                if hessian:
+                    H[hoff[r]:hoff[r + 1]] = Hr.ravel()
+        topo._dev.set_values(g, H)
 
     def sparse_hessians(self):
-        """`hessian()` as `sella_amd.linalg.SparseInternalHessians` (same rows: bonds, angles, dihedrals, then the
-        empty rotation rows), the blocks evaluated on the device straight into its buffers (internal.py:2189-2305)."""
+        """`hessian()` as `sella_amd.linalg.SparseInternalHessians` (same rows: translations, bonds, angles, dihedrals,
+        rotations), the blocks evaluated on the device straight into its buffers (internal.py:2189-2305)."""
         from .linalg import SparseInternalHessians
-        sk = self._sparse_topology('h', self.nrotations)
+        sk = self._sparse_topology('h')
         H = SparseInternalHessians._filled(sk, self.ndof)
         self._sparse_fill(sk, hessian=True)
         return H
@@ -720,7 +851,7 @@ class InternalCoordinates:
     def sparse_jacobian(self):
         """`jacobian()` as `sella_amd.linalg.SparseInternalJacobian`, the gradient blocks evaluated on the device."""
         from .linalg import SparseInternalJacobian
-        topo = self._sparse_topology('g', 0)
+        topo = self._sparse_topology('g')
         J = SparseInternalJacobian._filled(topo)
         self._sparse_fill(topo, hessian=False)
         return J
@@ -786,8 +917,8 @@ def covalent_radius(symbol, default=1.0):
 
 
 def _ic_counts(self):
-    return dict(ntrans=0, nbonds=len(self.idx['bonds']), nangles=len(self.idx['angles']),
-                ndihedrals=len(self.idx['dihedrals']), nother=0, nrotations=0)
+    return dict(ntrans=len(self.trans), nbonds=len(self.idx['bonds']), nangles=len(self.idx['angles']),
+                ndihedrals=len(self.idx['dihedrals']), nother=0, nrotations=len(self.rot))
 
 
 for _name in ('ntrans', 'nbonds', 'nangles', 'ndihedrals', 'nother', 'nrotations'):
@@ -797,6 +928,12 @@ for _name in ('ntrans', 'nbonds', 'nangles', 'ndihedrals', 'nother', 'nrotations
 def _ic_copy(self):
     new = InternalCoordinates(self.atoms, self.idx['bonds'], self.idx['angles'], self.idx['dihedrals'],
                               self.ncv['bonds'], self.ncv['angles'], self.ncv['dihedrals'])
+    new.trans = [(ix.copy(), d) for ix, d in self.trans]
+    new.frags = [ix.copy() for ix in self.frags]
+    new.frag_ref = [ref.copy() for ref in self.frag_ref]
+    new.frag_q = self.frag_q.copy()
+    new.rot = list(self.rot)
+    new.allow_fragments = self.allow_fragments
     new.cons = self.cons.copy() if getattr(self, 'cons', None) is not None else None
     return new
 
@@ -807,11 +944,13 @@ def _ic_radii(self):
 
 def _ic_guess_hessian(self, diagonal_only=False):
     """Diagonal model Hessian in the internal coordinates (internal.py:3738-3820: the Schlegel-type
-    exponential formulas of `_h0_bond`, `_h0_angle`, `_h0_dihedral`)."""
+    exponential formulas of `_h0_bond`, `_h0_angle`, `_h0_dihedral`; translations and rotations 0.05 Hartree when
+    fragments are allowed, 70 otherwise)."""
     rc = _ic_radii(self)
-    q = self.calc()
+    nt, nr = self.ntrans, self.nrotations
+    q = self.calc()[nt:self.nint - nr]
     nb, na, nd = self.nbonds, self.nangles, self.ndihedrals
-    h0 = np.zeros(self.nint)
+    h0 = np.zeros(nb + na + nd)
     b = self.idx['bonds']
     rcov = rc[b].sum(axis=1) if nb else np.zeros(0)
     h0[:nb] = 0.3601 * np.exp(-1.944 * (q[:nb] - rcov) / _BOHR) * _HARTREE / _BOHR ** 2
@@ -832,6 +971,9 @@ def _ic_guess_hessian(self, diagonal_only=False):
         L = nbonds_of[d[:, 1]] + nbonds_of[d[:, 2]] - 2
         h0[nb + na:] = (0.0015 + 14.0 * np.maximum(L, 0) ** 0.57 * np.exp(-2.85 * (rbc - cbc) / _BOHR)
                         / (rbc * cbc / _BOHR ** 2) ** 4.00) * _HARTREE
+    if nt or nr:
+        hf = 0.05 * _HARTREE if self.allow_fragments else 70.0
+        h0 = np.concatenate([np.full(nt, hf), h0, np.full(nr, hf)])
     return np.abs(h0) if diagonal_only else np.diag(np.abs(h0))
 
 
@@ -862,11 +1004,14 @@ def _fragments(natoms, bonds):
     return np.array([find(i) for i in range(natoms)])
 
 
-def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15.):
+def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., allow_fragments=False):
     """Automatic redundant internals, the topology search of sella/internal.py:3366-3671 as array code:
 
     * bonds: pairs closer than scale * (r_cov,i + r_cov,j); while the bond graph is disconnected the scale grows by
       5 % and bonds BETWEEN fragments are added (`find_all_bonds`, :3366-3423; minimum-image convention);
+      with `allow_fragments` the bonds of the first scale are kept as they are, and each disconnected fragment gets
+      three translations (its centroid) and, with two atoms or more, three rotations (:3424-3455; the lone atoms'
+      translations first, then per fragment in order of its lowest atom index);
     * angles: every pair of bonds at an atom whose angle lies in (atol, pi - atol), atol = 15 degrees; a (nearly)
       linear one at an atom with a third neighbour is replaced by the improper dihedral through that neighbour
       (`find_all_angles`, :3458-3573; the two-neighbour case needs a dummy atom there — out of scope, the angle
@@ -884,7 +1029,7 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15.):
         dist = np.linalg.norm(pos[allp[:, 1]] - pos[allp[:, 0]] + allv[:, 0] @ cell, axis=1)
         reach = rc[allp[:, 0]] + rc[allp[:, 1]]
         have = dist <= scale * reach
-        for _ in range(200):
+        for _ in range(0 if allow_fragments else 200):
             labels = _fragments(natoms, allp[have])
             if len(np.unique(labels)) == 1:
                 break
@@ -947,6 +1092,20 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15.):
     dncv = np.array(dv, dtype=np.float64) if dl else np.zeros((0, 3, 3))
     ic = cls(atoms, bonds=bonds, angles=angles, dihedrals=dih, bond_ncvecs=bncv, angle_ncvecs=ancv,
              dihedral_ncvecs=dncv)
+    if allow_fragments:
+        ic.allow_fragments = True
+        labels = _fragments(natoms, bonds)
+        if len(np.unique(labels)) > 1:
+            if np.any(atoms.pbc):
+                raise NotImplementedError('fragment coordinates of periodic systems (the reference unwraps each '
+                                          'fragment across the cell, internal.py:3440-3455) are not supported')
+            lone = np.bincount(bonds.ravel(), minlength=natoms) == 0 if len(bonds) else np.ones(natoms, dtype=bool)
+            for i in np.flatnonzero(lone):
+                ic.add_translation(int(i))
+            for lab in np.unique(labels[~lone]):
+                group = np.flatnonzero(labels == lab)
+                ic.add_translation(group)
+                ic.add_rotation(group)
     ic.cons = cons if cons is not None else Constraints(atoms)
     return ic
 

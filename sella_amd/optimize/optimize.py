@@ -5,7 +5,8 @@ trust-radius rules of `step()` (:359-434).
 
 `internal=True` (or an `InternalCoordinates` object) selects `InternalPES` (geodesic steps in redundant
 internal coordinates).  Options outside the saddle-point scope raise NotImplementedError:
-`optimize_cell=True` (Cell*PES).
+`optimize_cell=True` (Cell*PES).  `allow_fragments=True` with internal coordinates describes disconnected fragments by
+TRIC translations and rotations (internal.py:3366-3455) instead of bonds between them.
 """
 import warnings
 from time import localtime, strftime
@@ -40,9 +41,9 @@ class Sella(Optimizer):
         # saddle-point path are refused.
         if optimize_cell:
             raise NotImplementedError('optimize_cell requires order=0 and is outside the saddle-point scope')
-        if allow_fragments:
-            raise NotImplementedError('allow_fragments needs the TRIC translation / rotation coordinates, which '
-                                      'are outside the saddle-point scope (DESIGN.md section 7)')
+        # allow_fragments: disconnected fragments get TRIC translations and rotations instead of artificial bonds
+        # between them (internal coordinates only; accepted and ignored in Cartesian coordinates, as the reference)
+        self.allow_fragments = bool(allow_fragments)
         # the reference integrates the exact geodesic unless told otherwise (optimize.py:125)
         self.exact_geodesic = exact_geodesic is None or bool(exact_geodesic)
         self.optimize_cell = False
@@ -219,7 +220,8 @@ class Sella(Optimizer):
                                      "Internals object.")
                 auto = False
             else:
-                internal = InternalCoordinates.from_atoms(atoms, cons=constraints)
+                internal = InternalCoordinates.from_atoms(atoms, cons=constraints,
+                                                          allow_fragments=getattr(self, 'allow_fragments', False))
                 auto = True
             self.internal = internal.copy()
             self.constraints = None

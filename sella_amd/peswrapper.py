@@ -875,9 +875,11 @@ class InternalPES(PES):
         x = self.int.calc()
         nd = self.int.ndihedrals
         if self.curr['x'] is not None and nd:
-            # keep dihedrals continuous with the previous point instead of jumping by 2 pi (:996-1008)
-            dx = x[-nd:] - self.curr['x'][-nd:]
-            x[-nd:] = self.curr['x'][-nd:] + (dx + np.pi) % (2 * np.pi) - np.pi
+            # keep dihedrals continuous with the previous point instead of jumping by 2 pi (:996-1008); they sit
+            # between the angles and the rotations
+            sl = self.int._dihedral_slice()
+            dx = x[sl] - self.curr['x'][sl]
+            x[sl] = self.curr['x'][sl] + (dx + np.pi) % (2 * np.pi) - np.pi
         return x
 
     def wrap_dx(self, dx):
