@@ -6,14 +6,17 @@ sella/internal.py the saddle-point path needs:
     `_dihedral_value`) and internal.py:466-470 (`_translation`);
   * `Constraints`: fix_translation / fix_bond / fix_angle / fix_dihedral with eq / lt / gt kinds,
     `residual()`, `jacobian()` (dense, internal.py:1780-1902), `hessian().ldot(L)`
-    (internal.py:2189-2305, linalg.py:601-618), inequality bookkeeping (internal.py:2788-2823).
+    (internal.py:2189-2305, linalg.py:601-618), inequality bookkeeping (internal.py:2788-2823);
+  * dummy atoms (internal.py:1214-1336, 3458-3545): fictitious points the coordinate system carries at linear centres
+    with two neighbours.  Every coordinate is evaluated over the extended positions [atoms; dummies], and the calculator
+    never sees them.
 
 The reference differentiates these functions with JAX (CPU).  Here the derivatives are exact
 too: second-order forward-mode (hyper-dual) arithmetic inside one HIP kernel per coordinate kind
 (csrc/internals.hip), one thread per (coordinate, component) — no JAX.  TRIC fragment coordinates (translations of a
 fragment's centroid, rotations as the exponential map of its best-aligning quaternion, internal.py:1030-1078) are part of
 `InternalCoordinates`; the rotations are evaluated in closed form by csrc/tric.hip.  Out of scope here:
-cell derivatives, dummy atoms.
+cell derivatives.
 """
 from functools import partialmethod
 
@@ -79,8 +82,9 @@ class Coordinate:
     def __repr__(self):
         return f'{self.__class__.__name__}({self.indices.tolist()})'
 
-    def calc(self, atoms):
-        pos = atoms.positions[self.indices][None]
+    def calc(self, atoms, positions=None):
+        """Value at the geometry of `atoms`, or at `positions` (the extended array [atoms; dummies]) when given."""
+        pos = (atoms.positions if positions is None else positions)[self.indices][None]
         tv = (self.ncvecs @ np.asarray(atoms.cell, dtype=float))[None]
         return float(evaluate_kind(self.kind, pos, tv)[0][0])
 
@@ -118,8 +122,8 @@ class Translation(Coordinate):
         """What `__eq__` compares, hashable (Constraints._add)."""
         return (self.kwargs['dim'], frozenset(self.indices.tolist()))
 
-    def calc(self, atoms):
-        return float(atoms.positions[self.indices, self.kwargs['dim']].mean())
+    def calc(self, atoms, positions=None):
+        return float((atoms.positions if positions is None else positions)[self.indices, self.kwargs['dim']].mean())
 
 
 class RotationGenerator(Coordinate):
@@ -141,17 +145,19 @@ class RotationGenerator(Coordinate):
     def __repr__(self):
         return f'RotationGenerator(axis={self.kwargs["axis"]}, natoms={len(self.indices)})'
 
-    def calc(self, atoms):
+    def calc(self, atoms, positions=None):
         return 0.0
 
-    def generator(self, atoms):
-        """(1, 3N) row: d(theta_axis)/dx for a rigid rotation, unit norm (zero row for a degenerate group)."""
-        pos = np.asarray(atoms.positions, dtype=np.float64)[self.indices]
+    def generator(self, atoms, positions=None):
+        """(1, 3n) row: d(theta_axis)/dx for a rigid rotation, unit norm (zero row for a degenerate group); n atoms, or
+        n = len(positions) when the extended positions [atoms; dummies] are given."""
+        allpos = np.asarray(atoms.positions if positions is None else positions, dtype=np.float64)
+        pos = allpos[self.indices]
         rel = pos - pos.mean(axis=0)
         e = np.zeros(3)
         e[self.kwargs['axis']] = 1.0
         g = np.cross(e, rel)
-        row = np.zeros((1, 3 * len(atoms)))
+        row = np.zeros((1, 3 * len(allpos)))
         row[0, (3 * self.indices[:, None] + np.arange(3)[None, :]).ravel()] = g.ravel()
         nrm = np.linalg.norm(row)
         return row / nrm if nrm > 1e-12 else row
@@ -258,11 +264,36 @@ class _JacobianStack:
         return out
 
 
+class DummyAtoms:
+    """The dummy atoms of one coordinate system: positions (D, 3).  One object is shared by an `InternalCoordinates`
+    and its `Constraints`, so that moving the dummies moves them for both (the reference shares an ASE Atoms of
+    'X' atoms the same way, internal.py:1214-1336)."""
+
+    def __init__(self, positions=None):
+        self.positions = np.zeros((0, 3)) if positions is None else np.array(positions, dtype=np.float64).reshape(-1, 3)
+
+    def __len__(self):
+        return len(self.positions)
+
+    def copy(self):
+        return DummyAtoms(self.positions)
+
+
+def _extended(atoms, dummies):
+    """[atoms; dummies] positions: the atoms' own array when there are no dummies."""
+    d = dummies.positions
+    return atoms.positions if len(d) == 0 else np.vstack([atoms.positions, d])
+
+
 class Constraints:
     _names = ('translations', 'bonds', 'angles', 'dihedrals', 'other', 'rotations')
 
     def __init__(self, atoms, dummies=None, dinds=None, ignore_rotation=True):
+        """`dummies`: a `DummyAtoms` shared with the coordinate system (or a (D, 3) array): constraints may name a dummy
+        by its index N + k, and the constraint Jacobian has 3 (N + D) columns.  `dinds` is accepted for the
+        reference's signature; which atom a dummy belongs to is the coordinate system's business."""
         self.atoms = atoms
+        self.dummies = dummies if isinstance(dummies, DummyAtoms) else DummyAtoms(dummies)
         self.internals = {k: [] for k in self._names}
         self._targets = {k: [] for k in self._names}
         self._active = {k: [] for k in self._names}
@@ -292,8 +323,16 @@ class Constraints:
         return len(self.atoms)
 
     @property
+    def ndummies(self):
+        return len(self.dummies)
+
+    @property
+    def all_positions(self):
+        return _extended(self.atoms, self.dummies)
+
+    @property
     def ndof(self):
-        return 3 * self.natoms
+        return 3 * (self.natoms + self.ndummies)
 
     def _count(self, name):
         return self._memo(('count', name), lambda: int(sum(self._active[name])))
@@ -309,8 +348,10 @@ class Constraints:
     def nint(self):
         return self.ntrans + self.nbonds + self.nangles + self.ndihedrals + self.nrotations
 
-    def copy(self):
-        new = self.__class__(self.atoms, ignore_rotation=self.ignore_rotation)
+    def copy(self, dummies=None):
+        """A copy with its own constraint lists; it shares the atoms and — unless `dummies` is given — the dummies."""
+        new = self.__class__(self.atoms, dummies=self.dummies if dummies is None else dummies,
+                             ignore_rotation=self.ignore_rotation)
         for name in self._names:
             new.internals[name] = list(self.internals[name])
             new._targets[name] = list(self._targets[name])
@@ -337,7 +378,7 @@ class Constraints:
         na = _NATOMS[name]
         idx = np.array([c.indices for c in coords], dtype=np.int64).reshape((len(coords), na))
         ncv = np.array([c.ncvecs for c in coords], dtype=np.float64).reshape((len(coords), na - 1, 3))
-        pos = self.atoms.positions[idx] if len(coords) else np.zeros((0, na, 3))
+        pos = self.all_positions[idx] if len(coords) else np.zeros((0, na, 3))
         tvec = ncv @ np.asarray(self.atoms.cell, dtype=float)
         return idx, pos, tvec
 
@@ -360,7 +401,7 @@ class Constraints:
 
     def calc(self):
         rows, dofs, wts, nt = self._translation_arrays()
-        x = self.atoms.positions.ravel()
+        x = self.all_positions.ravel()
         vals = [np.bincount(rows, weights=wts * x[dofs], minlength=nt) if nt else np.zeros(0)]
         for name in ('bonds', 'angles', 'dihedrals'):
             idx, pos, tvec = self._gather(name)
@@ -409,7 +450,8 @@ class Constraints:
             J = np.vstack([J, block])
         rot = self._active_list('rotations')
         if rot:
-            J = np.vstack([J] + [r.generator(self.atoms) for r in rot])
+            allpos = self.all_positions
+            J = np.vstack([J] + [r.generator(self.atoms, allpos) for r in rot])
         return J
 
     def hessian(self):
@@ -439,9 +481,9 @@ class Constraints:
             return
         for name in self._names:
             for i, (coord, kind, target) in enumerate(zip(self.internals[name], self._kind[name], self._targets[name])):
-                if kind == 'lt' and coord.calc(self.atoms) <= target:
+                if kind == 'lt' and coord.calc(self.atoms, self.all_positions) <= target:
                     self._set_active(name, i, False)
-                elif kind == 'gt' and coord.calc(self.atoms) >= target:
+                elif kind == 'gt' and coord.calc(self.atoms, self.all_positions) >= target:
                     self._set_active(name, i, False)
                 else:
                     self._set_active(name, i, True)
@@ -454,7 +496,7 @@ class Constraints:
             for i, (coord, kind, target) in enumerate(zip(self.internals[name], self._kind[name], self._targets[name])):
                 if self._active[name][i]:
                     continue
-                val = coord.calc(self.atoms)
+                val = coord.calc(self.atoms, self.all_positions)
                 if (kind == 'lt' and val > target) or (kind == 'gt' and val < target):
                     self._set_active(name, i, True)
                     all_valid = False
@@ -518,7 +560,7 @@ class Constraints:
                 return
             new = Translation(index, dim)
         if target is None:
-            target = new.calc(self.atoms)
+            target = new.calc(self.atoms, self.all_positions)
         self._add('translations', new, target, 'eq', replace_ok)
 
     def fix_rotation(self, indices=None, axis=None):
@@ -537,7 +579,7 @@ class Constraints:
     def _fix_internal(self, cls, name, conv, indices, ncvecs=None, mic=None, target=None,
                       comparator='eq', replace_ok=True):
         new = indices if isinstance(indices, cls) else cls(indices, ncvecs=ncvecs)
-        target = new.calc(self.atoms) if target is None else target * conv
+        target = new.calc(self.atoms, self.all_positions) if target is None else target * conv
         self._add(name, new, target, comparator, replace_ok)
 
     fix_bond = partialmethod(_fix_internal, Bond, 'bonds', 1.)
@@ -576,7 +618,12 @@ class InternalCoordinates:
     position along one axis: linear, rows of weight 1/m, no curvature); rotations are `rot` [(fragment, axis)] over
     the fragments `frags` (atom indices) with their centred reference positions `frag_ref` and quaternion state
     `frag_q (nfrag, 4)` (csrc/tric.hip).  Order of the coordinates, the reference's: translations, bonds, angles,
-    dihedrals, rotations.  Dummy atoms are not part of this class.
+    dihedrals, rotations.
+
+    Dummy atoms (internal.py:1214-1336): `dummies (D, 3)` are fictitious points numbered N, ..., N + D - 1 after the
+    N real atoms, `dinds` (N,) names the dummy of each atom (-1: none).  Every coordinate is evaluated over
+    `all_positions` = [atoms; dummies], and the Cartesian side of every Jacobian and Hessian has `ndof` = 3 (N + D)
+    entries.  `add_dummy` adds one.
     """
     _order = ('bonds', 'angles', 'dihedrals')
 
@@ -595,8 +642,51 @@ class InternalCoordinates:
         self.frag_q = np.zeros((0, 4))        # quaternion state per fragment (read and written by every evaluation)
         self.rot = []                         # [(fragment, axis)]
         self.allow_fragments = False          # guess_hessian: 0.05 Hartree for the fragment coordinates, as the reference
+        self._dummies = DummyAtoms()          # shared with `cons`
+        self.dinds = np.full(len(atoms), -1, dtype=np.int64)
 
-    ndof = property(lambda self: 3 * len(self.atoms))
+    # ---- dummy atoms (internal.py:1214-1336) ---------------------------------------------------------------------
+    @property
+    def dummies(self):
+        return self._dummies.positions
+
+    @dummies.setter
+    def dummies(self, value):
+        value = np.array(value, dtype=np.float64).reshape(-1, 3)
+        if len(value) != len(self._dummies):
+            raise ValueError(f'{len(self._dummies)} dummy positions expected, got {len(value)}')
+        self._dummies.positions = value
+
+    ndummies = property(lambda self: len(self._dummies))
+    ndof = property(lambda self: 3 * (len(self.atoms) + self.ndummies))
+    all_positions = property(lambda self: _extended(self.atoms, self._dummies))
+
+    def set_all_positions(self, pos):
+        """Move atoms and dummies to `pos` ((N + D) x 3 values, in the order of `all_positions`)."""
+        pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
+        n = len(self.atoms)
+        self.atoms.positions = pos[:n].copy()
+        if self.ndummies:
+            self._dummies.positions = pos[n:].copy()
+
+    def add_dummy(self, position, centre=None):
+        """Add a dummy atom at `position` (3,), optionally as the dummy of atom `centre`: returns its index N + k.
+        Coordinates that use it are added as usual (`add_*`, or index arrays given to the constructor).  A `cons`
+        that does not share this object's dummies is replaced by a copy that does (the caller's object is not
+        changed)."""
+        n = len(self.atoms)
+        k = n + self.ndummies
+        if centre is not None:
+            if not 0 <= int(centre) < n:
+                raise ValueError(f'dummy centre {centre} is not a real atom')
+            if self.dinds[int(centre)] >= 0:
+                raise DuplicateInternalError(f'atom {centre} has a dummy already ({self.dinds[int(centre)]})')
+        self._dummies.positions = np.vstack([self._dummies.positions, np.asarray(position, dtype=np.float64).reshape(1, 3)])
+        if centre is not None:
+            self.dinds[int(centre)] = k
+        if self.cons is not None and self.cons.dummies is not self._dummies:
+            self.cons = self.cons.copy(dummies=self._dummies)
+        return k
     nint = property(lambda self: sum(len(self.idx[k]) for k in self._order) + len(self.trans) + len(self.rot))
 
     # ---- TRIC fragment coordinates (internal.py:3085-3144) -----------------------------------------------------
@@ -624,7 +714,7 @@ class InternalCoordinates:
             return
         frag = next((f for f, fx in enumerate(self.frags) if np.array_equal(fx, ix)), None)
         if frag is None:
-            ref = np.array(self.atoms.positions[ix], dtype=np.float64)
+            ref = np.array(self.all_positions[ix], dtype=np.float64)
             self.frags.append(ix)
             self.frag_ref.append(ref - ref.mean(axis=0))
             self.frag_q = np.vstack([self.frag_q, [1.0, 0.0, 0.0, 0.0]])
@@ -639,13 +729,13 @@ class InternalCoordinates:
 
     def _rot_eval(self, tangent=None, hessian=False):
         """One device call for every fragment (csrc/tric.hip; updates `frag_q`): values (nrot,) and per rotation row
-        its dofs (3m,), gradient (3m,), H t (3m,) when `tangent` (3N,) is given, Hessian (3m, 3m) when `hessian`."""
+        its dofs (3m,), gradient (3m,), H t (3m,) when `tangent` (ndof,) is given, Hessian (3m, 3m) when `hessian`."""
         if not self.rot:
             return np.zeros(0), []
         sizes = np.array([len(ix) for ix in self.frags], dtype=np.int64)
         fp = np.concatenate([[0], np.cumsum(sizes)])
         tan = None if tangent is None else np.asarray(tangent, dtype=np.float64).reshape(-1, 3)
-        val, g, hv, H = get_context().tric_eval(fp, np.concatenate(self.frags), self.atoms.positions,
+        val, g, hv, H = get_context().tric_eval(fp, np.concatenate(self.frags), self.all_positions,
                                                 np.concatenate(self.frag_ref), self.frag_q, tangent=tan,
                                                 hessian=hessian)
         hoff = np.concatenate([[0], np.cumsum(27 * sizes * sizes)])
@@ -671,14 +761,14 @@ class InternalCoordinates:
 
     def _batch(self, name):
         idx = self.idx[name]
-        pos = self.atoms.positions[idx]
+        pos = self.all_positions[idx]
         tvec = self.ncv[name] @ np.asarray(self.atoms.cell, dtype=np.float64)
         dofs = (3 * idx[:, :, None] + np.arange(3)[None, None, :]).reshape(len(idx), 3 * _NATOMS[name])
         return pos, tvec, dofs
 
     def calc(self):
-        """q(x) (internal.py:1735-1778)."""
-        x = self.atoms.positions.ravel()
+        """q(x) (internal.py:1735-1778), x = `all_positions`."""
+        x = self.all_positions.ravel()
         tq = [np.array([w @ x[d] for d, w in self._trans_rows()])] if self.trans else []
         rq = [self._rot_eval()[0]] if self.rot else []
         return np.concatenate(tq + [evaluate_kind(k, *self._batch(k)[:2], hessian=False)[0] for k in self._order] + rq)
@@ -709,7 +799,7 @@ class InternalCoordinates:
         return _JacobianStack(self.ndof, blocks)
 
     def jacobian(self):
-        """Dense Wilson B-matrix dq/dx, (nint, 3N) (internal.py:1780-1902)."""
+        """Dense Wilson B-matrix dq/dx, (nint, 3(N + D)) (internal.py:1780-1902)."""
         return self.jacobian_blocks().asarray()
 
     def jacobian_csr(self):
@@ -740,7 +830,7 @@ class InternalCoordinates:
         return csr_matrix((np.concatenate(data), np.concatenate(cols), indptr), shape=(self.nint, self.ndof))
 
     def hessian_rdot_mult(self, v, W):
-        """D(v) @ W for W (3N, k) without forming D(v): (nint, k)."""
+        """D(v) @ W for W (ndof, k) without forming D(v): (nint, k)."""
         v = np.asarray(v, dtype=np.float64).ravel()
         W = np.asarray(W, dtype=np.float64).reshape(self.ndof, -1)
         out = np.zeros((self.nint, W.shape[1]))
@@ -760,7 +850,7 @@ class InternalCoordinates:
         return out
 
     def hessian_rdot(self, v):
-        """D(v)_i = H_i v as a dense (nint, 3N) matrix (internal.py:2307-2575: one HVP per coordinate, from the
+        """D(v)_i = H_i v as a dense (nint, ndof) matrix (internal.py:2307-2575: one HVP per coordinate, from the
         device's Hessian-vector kernel; the scatter is `_JacobianStack`'s)."""
         v = np.asarray(v, dtype=np.float64).ravel()
         nt = len(self.trans)
@@ -797,7 +887,8 @@ class InternalCoordinates:
         from .linalg import SparseInternalHessiansSkeleton, _SparseTopology
         tix = [ix for ix, _ in self.trans]
         rix = [self.frags[f] for f, _ in self.rot]
-        key = ((len(self.atoms),) + tuple(self.idx[k].tobytes() for k in self._order)
+        npts = len(self.atoms) + self.ndummies
+        key = ((npts,) + tuple(self.idx[k].tobytes() for k in self._order)
                + (tuple(ix.tobytes() for ix in tix), tuple(ix.tobytes() for ix in rix)))
         cache = self.__dict__.setdefault('_sparse_topo', {})
         hit = cache.get(kind)
@@ -805,9 +896,9 @@ class InternalCoordinates:
             return hit[1]
         indices = tix + [ix for k in self._order for ix in self.idx[k]] + rix
         if kind == 'h':
-            topo = SparseInternalHessiansSkeleton._from_indices(len(self.atoms), indices)
+            topo = SparseInternalHessiansSkeleton._from_indices(npts, indices)
         else:
-            topo = _SparseTopology(len(self.atoms), indices)
+            topo = _SparseTopology(npts, indices)
         cache[kind] = (key, topo)
         return topo
 
@@ -934,18 +1025,24 @@ def _ic_copy(self):
     new.frag_q = self.frag_q.copy()
     new.rot = list(self.rot)
     new.allow_fragments = self.allow_fragments
-    new.cons = self.cons.copy() if getattr(self, 'cons', None) is not None else None
+    new._dummies = self._dummies.copy()
+    new.dinds = self.dinds.copy()
+    new.cons = self.cons.copy(dummies=new._dummies) if getattr(self, 'cons', None) is not None else None
     return new
 
 
+_RCOV_DUMMY = 0.2             # ase.data.covalent_radii of 'X', what the reference's dummies carry
+
+
 def _ic_radii(self):
-    return np.array([covalent_radius(s) for s in self.atoms.symbols])
+    rc = np.array([covalent_radius(s) for s in self.atoms.symbols])
+    return np.concatenate([rc, np.full(self.ndummies, _RCOV_DUMMY)]) if self.ndummies else rc
 
 
 def _ic_guess_hessian(self, diagonal_only=False):
     """Diagonal model Hessian in the internal coordinates (internal.py:3738-3820: the Schlegel-type
     exponential formulas of `_h0_bond`, `_h0_angle`, `_h0_dihedral`; translations and rotations 0.05 Hartree when
-    fragments are allowed, 70 otherwise)."""
+    fragments are allowed, 70 otherwise; a dihedral through a dummy atom 0.5 Hartree, :3808-3811)."""
     rc = _ic_radii(self)
     nt, nr = self.ntrans, self.nrotations
     q = self.calc()[nt:self.nint - nr]
@@ -954,7 +1051,8 @@ def _ic_guess_hessian(self, diagonal_only=False):
     b = self.idx['bonds']
     rcov = rc[b].sum(axis=1) if nb else np.zeros(0)
     h0[:nb] = 0.3601 * np.exp(-1.944 * (q[:nb] - rcov) / _BOHR) * _HARTREE / _BOHR ** 2
-    nbonds_of = np.bincount(b.ravel(), minlength=len(self.atoms)) if nb else np.zeros(len(self.atoms), dtype=int)
+    npts = len(self.atoms) + self.ndummies
+    nbonds_of = np.bincount(b.ravel(), minlength=npts) if nb else np.zeros(npts, dtype=int)
     if na:
         a = self.idx['angles']
         pa, ta, _ = self._batch('angles')
@@ -971,6 +1069,8 @@ def _ic_guess_hessian(self, diagonal_only=False):
         L = nbonds_of[d[:, 1]] + nbonds_of[d[:, 2]] - 2
         h0[nb + na:] = (0.0015 + 14.0 * np.maximum(L, 0) ** 0.57 * np.exp(-2.85 * (rbc - cbc) / _BOHR)
                         / (rbc * cbc / _BOHR ** 2) ** 4.00) * _HARTREE
+        if self.ndummies:
+            h0[nb + na:][np.any(d >= len(self.atoms), axis=1)] = 0.5 * _HARTREE
     if nt or nr:
         hf = 0.05 * _HARTREE if self.allow_fragments else 70.0
         h0 = np.concatenate([np.full(nt, hf), h0, np.full(nr, hf)])
@@ -1014,8 +1114,16 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
       translations first, then per fragment in order of its lowest atom index);
     * angles: every pair of bonds at an atom whose angle lies in (atol, pi - atol), atol = 15 degrees; a (nearly)
       linear one at an atom with a third neighbour is replaced by the improper dihedral through that neighbour
-      (`find_all_angles`, :3458-3573; the two-neighbour case needs a dummy atom there — out of scope, the angle
-      is simply left out);
+      (`find_all_angles`, :3458-3573);
+    * dummy atoms (:3480-3545): a (nearly) linear centre c with exactly two neighbours gets a dummy atom X at unit
+      distance, along the normalised cross product of its two bond directions (bonds sorted by length, n1 the nearer
+      neighbour; when the product is below 1e-4, the Cartesian axis least aligned with the shorter bond,
+      orthogonalised).  The coordinates gain the bond c-X, the angles n-c-X that lie in (atol, pi - atol) and the
+      improper dihedral n1-c-X-n2; the constraints gain c-X and n1-c-X, fixed at their values (only one of the two
+      supplementary angles: both would over-constrain the real atoms).  Centres are taken in atom order; the dummy
+      bonds follow the real bonds, a dummy's angles and improper take their centre's place in the angle and
+      dihedral order.  A centre with a bond grown to connect fragments (a contact such as a hydrogen bond) gets no
+      dummy: its linear angle is left out.  With dummies, a caller's `cons` is copied, not changed;
     * dihedrals: every chain a-b-c-d of two kept angles sharing the bond b-c (`find_all_dihedrals`, :3575-3600), plus
       one improper n0-c-n1-n2 for centres with 3 or 4 neighbours that no proper dihedral passes through
       (:3602-3660: keeps the Jacobian well conditioned at planar geometries)."""
@@ -1029,6 +1137,7 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
         dist = np.linalg.norm(pos[allp[:, 1]] - pos[allp[:, 0]] + allv[:, 0] @ cell, axis=1)
         reach = rc[allp[:, 0]] + rc[allp[:, 1]]
         have = dist <= scale * reach
+        covalent = have.copy()                                           # the bonds of the first scale
         for _ in range(0 if allow_fragments else 200):
             labels = _fragments(natoms, allp[have])
             if len(np.unique(labels)) == 1:
@@ -1036,10 +1145,13 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
             scale *= 1.05
             have |= (labels[allp[:, 0]] != labels[allp[:, 1]]) & (dist <= scale * reach)
         bonds, bncv = allp[have], allv[have]
+        ncov = np.bincount(allp[covalent].ravel(), minlength=natoms)        # covalent bonds per atom
     else:
         bonds, bncv = np.zeros((0, 2), dtype=np.int64), np.zeros((0, 1, 3))
+        ncov = np.zeros(natoms, dtype=np.int64)
     angles, ancv = angles_from_bonds(bonds, bncv)
     dl, dv, seen = [], [], set()
+    dummies = []                # per dummy: (centre, position, neighbours [(atom, image offset)] shorter bond first)
 
     def add_dihedral(idx4, ncv3):
         a, b2, c, d = (int(v) for v in idx4)
@@ -1057,8 +1169,24 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
         for (i, j), v in zip(bonds, bncv[:, 0]):
             nbrs[int(i)].append((int(j), v))
             nbrs[int(j)].append((int(i), -v))
-        if dihedrals:
-            for (n1, c, n2), (v1, v2) in zip(angles[~ok], ancv[~ok]):
+        dang, dancv = [], []
+        for (n1, c, n2), (v1, v2) in zip(angles[~ok], ancv[~ok]):
+            if len(nbrs[int(c)]) == 2 and ncov[int(c)] == 2:
+                # linear centre with two (covalent) neighbours: a dummy atom, :3480-3545
+                site, near = _dummy_site(pos, cell, int(c), nbrs[int(c)])
+                x = natoms + len(dummies)
+                dummies.append((int(c), site, near))
+                if dihedrals:
+                    (m1, w1), (m2, w2) = near
+                    add_dihedral((m1, c, x, m2), (-w1, np.zeros(3), w2))
+                for n, w in nbrs[int(c)]:
+                    r1, r2 = pos[int(c)] - pos[n] - w @ cell, site - pos[int(c)]
+                    val = np.arccos(np.clip(r1 @ r2 / (np.linalg.norm(r1) * np.linalg.norm(r2)), -1.0, 1.0))
+                    if atol < np.pi - val < np.pi - atol:            # the angle n-c-X itself is pi - val
+                        dang.append([n, int(c), x])
+                        dancv.append([-w, np.zeros(3)])
+                continue
+            if dihedrals:
                 # linear n1-c-n2 with a third neighbour n3: improper (n1, c, n3, n2), :3556-3573
                 for n3, v3 in nbrs[int(c)]:
                     if (n3 == n1 and np.array_equal(v3, -v1)) or (n3 == n2 and np.array_equal(v3, v2)):
@@ -1066,6 +1194,12 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
                     add_dihedral((n1, c, n3, n2), (v1, v3, v2 - v3))
                     break
         angles, ancv = angles[ok], ancv[ok]
+        if dang:
+            # a dummy's angles take their centre's place in the (by centre) angle order
+            angles = np.concatenate([angles, np.array(dang, dtype=np.int64)])
+            ancv = np.concatenate([ancv, np.array(dancv, dtype=np.float64)])
+            order = np.argsort(angles[:, 1], kind='stable')
+            angles, ancv = angles[order], ancv[order]
     if dihedrals and len(angles):
         # proper dihedrals: join angles (a, b, c) and (b, c, d) over the shared bond b-c with consistent images
         by_bond = {}
@@ -1090,8 +1224,21 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
                 add_dihedral((n0, centre, n1, n2), (-v0, v1, v2 - v1))
     dih = np.array(dl, dtype=np.int64) if dl else np.zeros((0, 4), dtype=np.int64)
     dncv = np.array(dv, dtype=np.float64) if dl else np.zeros((0, 3, 3))
+    real_bonds = bonds
+    if dummies:
+        dbonds = np.array([[c, natoms + k] for k, (c, _, _) in enumerate(dummies)], dtype=np.int64)
+        bonds = np.concatenate([bonds, dbonds])
+        bncv = np.concatenate([bncv, np.zeros((len(dbonds), 1, 3))])
     ic = cls(atoms, bonds=bonds, angles=angles, dihedrals=dih, bond_ncvecs=bncv, angle_ncvecs=ancv,
              dihedral_ncvecs=dncv)
+    ic.cons = cons if cons is not None else Constraints(atoms, dummies=ic._dummies)
+    for c, site, _ in dummies:
+        ic.add_dummy(site, centre=c)                       # (a caller's cons is replaced by a copy here)
+    for k, (c, _, near) in enumerate(dummies):
+        (m1, w1), _ = near
+        ic.cons.fix_bond((c, natoms + k), replace_ok=False)
+        ic.cons.fix_angle((m1, c, natoms + k), ncvecs=(-w1, np.zeros(3)), replace_ok=False)
+    bonds = real_bonds
     if allow_fragments:
         ic.allow_fragments = True
         labels = _fragments(natoms, bonds)
@@ -1104,10 +1251,35 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
                 ic.add_translation(int(i))
             for lab in np.unique(labels[~lone]):
                 group = np.flatnonzero(labels == lab)
-                ic.add_translation(group)
-                ic.add_rotation(group)
-    ic.cons = cons if cons is not None else Constraints(atoms)
+                # the dummies of the fragment's centres move with it (`add_dummy_to_internals`, :2708-2730)
+                group = np.concatenate([group, [natoms + k for k, (c, _, _) in enumerate(dummies) if labels[c] == lab]])
+                ic.add_translation(group.astype(np.int64))
+                ic.add_rotation(group.astype(np.int64))
     return ic
+
+
+def _dummy_site(pos, cell, c, nbrs):
+    """Position of the dummy atom of the linear centre c with neighbours nbrs [(atom, image offset)] and those
+    neighbours sorted by bond length, shorter first (stable on a tie), :3486-3517."""
+    ends = [pos[n] + w @ cell for n, w in nbrs]
+    lengths = [np.linalg.norm(e - pos[c]) for e in ends]
+    order = np.argsort(lengths, kind='stable')
+    near = [nbrs[i] for i in order]
+    dx1 = pos[c] - ends[order[0]]
+    dx1 = dx1 / np.linalg.norm(dx1)
+    dx2 = ends[order[1]] - pos[c]
+    dx2 = dx2 / np.linalg.norm(dx2)
+    d = np.cross(dx1, dx2)
+    nrm = np.linalg.norm(d)
+    if nrm < 1e-4:
+        # (exactly) collinear: the Cartesian axis least aligned with the shorter bond, orthogonalised to it
+        d = np.zeros(3)
+        d[np.argmin(np.abs(dx1))] = 1.0
+        d = d - dx1 * (d @ dx1)
+        d = d / np.linalg.norm(d)
+    else:
+        d = d / nrm
+    return pos[c] + d, near
 
 
 InternalCoordinates.copy = _ic_copy

@@ -6,7 +6,8 @@ trust-radius rules of `step()` (:359-434).
 `internal=True` (or an `InternalCoordinates` object) selects `InternalPES` (geodesic steps in redundant
 internal coordinates).  Options outside the saddle-point scope raise NotImplementedError:
 `optimize_cell=True` (Cell*PES).  `allow_fragments=True` with internal coordinates describes disconnected fragments by
-TRIC translations and rotations (internal.py:3366-3455) instead of bonds between them.
+TRIC translations and rotations (internal.py:3366-3455) instead of bonds between them.  Linear centres with two
+neighbours get dummy atoms (internal.py:3480-3545); a rebuild of degraded internals places them anew.
 """
 import warnings
 from time import localtime, strftime
@@ -240,9 +241,12 @@ class Sella(Optimizer):
 
     # ---- restartable state (the reference has no resume) --------------------------------
     def save_state(self, filename):
-        """Everything the next step depends on besides the atoms: approximate Hessian, trust radius, schedule."""
+        """Everything the next step depends on besides the atoms: approximate Hessian, trust radius, schedule, and the
+        positions of the dummy atoms of internal coordinates."""
         H = self.pes.H
-        np.savez(filename, positions=self.pes.atoms.positions, B=(np.zeros((0, 0)) if H.B is None else H.B),
+        dpos = self.pes.dpos
+        np.savez(filename, positions=self.pes.atoms.positions, dummies=np.zeros((0, 3)) if dpos is None else dpos,
+                 B=(np.zeros((0, 0)) if H.B is None else H.B),
                  has_B=H.B is not None, H_initialized=H.initialized, delta=self.delta, rho=self.rho,
                  nsteps=self.nsteps, nsteps_since_diag=self.nsteps_since_diag, initialized=self.initialized,
                  first_diag=self.pes.first_diag)
@@ -250,6 +254,8 @@ class Sella(Optimizer):
     def load_state(self, filename):
         z = np.load(filename if str(filename).endswith('.npz') else str(filename) + '.npz')
         self.pes.atoms.positions = z['positions'].copy()
+        if self.pes.int is not None and 'dummies' in z.files and z['dummies'].shape == self.pes.int.dummies.shape:
+            self.pes.int.dummies = z['dummies'].copy()
         self.pes.set_H(z['B'].copy() if bool(z['has_B']) else None, initialized=bool(z['H_initialized']))
         self.delta, self.rho = float(z['delta']), float(z['rho'])
         self.nsteps, self.nsteps_since_diag = int(z['nsteps']), int(z['nsteps_since_diag'])

@@ -506,11 +506,13 @@ class PES:
 # InternalPES — optimisation in redundant internal coordinates with geodesic steps
 # (sella/peswrapper.py:609-1288; Hermes et al., J. Chem. Phys. 155, 094105 (2021)).
 #
-# Scope of this build: bonds / angles / dihedrals given as an `InternalCoordinates` object (or found
-# automatically from covalent radii), Cartesian constraints expressed through the usual `Constraints`
-# object.  Not built: dummy atoms and the re-generation of internals when an angle becomes linear
-# (`update_internals`, :1126-1172 — a RuntimeError is raised instead), the Newton "iterative stepper"
-# shortcut (:742-838; the ODE path it falls back to is the one implemented), cell degrees of freedom.
+# Scope of this build: translations / bonds / angles / dihedrals / rotations given as an `InternalCoordinates`
+# object (or found automatically from covalent radii), Cartesian constraints expressed through the usual
+# `Constraints` object.  Dummy atoms at linear centres are extra Cartesian degrees of freedom of this class
+# (:641-667, 756-834, 967-991, 1124-1127): the Cartesian vector is [atoms; dummies], 3 (N + D) long; the
+# calculator, the trajectory, the forces and `converged()` concern the N real atoms.  Not built: carrying the
+# approximate Hessian across a re-generation of the internals (`update_internals`, :1126-1172 — `Sella` builds a
+# fresh PES instead), cell degrees of freedom.
 # The heavy pieces run on the device: B-matrix rows and D(v) = H_i v (csrc/internals.hip), the range basis
 # and pseudo-inverse of B through the device eigensolver (`_BFactor`, in place of the reference's
 # `_gpu_qr` + SVD, :691-709), the Hessian algebra as for `PES`.
@@ -706,7 +708,7 @@ class InternalPES(PES):
         self.int_orig = internals
         new_int = internals.copy()
         if new_int.cons is None:
-            new_int.cons = Constraints(atoms)
+            new_int.cons = Constraints(atoms, dummies=new_int._dummies)
         kwargs.pop('constraints', None)
         # global translations / rotations are never projected out in internal space (peswrapper.py:633-641): a
         # caller's `Sella(internal=True, proj_rot=...)` must not collide with the explicit keywords below
@@ -744,13 +746,31 @@ class InternalPES(PES):
     def _get_Binv(self):
         return self._get_factor().pinv()
 
+    # ---- dummy atoms: extra Cartesian degrees of freedom (:641-667, 872-875) -------------------------------------
+    dpos = property(lambda self: None if self.int is None else self.int.dummies.copy())
+
+    def _state_hash(self):
+        h = PES._state_hash(self)
+        if self.int is not None and self.int.ndummies:
+            h += np.ascontiguousarray(self.int.dummies).tobytes()
+        return h
+
+    def restore(self):
+        PES.restore(self)
+        kept = self.savepoint.get('dpos')
+        if kept is not None and len(kept):
+            self.int.dummies = kept
+
+    def _all_positions(self):
+        return np.array(self.int.all_positions, dtype=np.float64)
+
     # ---- geodesic position update (:840-880, :1200-1221) ----------------------------------------------
     def _q_ode(self, t, y):
-        nx = 3 * len(self.atoms)
+        nx = self.int.ndof
         x, dxdt, g = y.reshape((3, nx))
         dydt = np.zeros((3, nx))
         dydt[0] = dxdt
-        self.atoms.positions = x.reshape((-1, 3)).copy()
+        self.int.set_all_positions(x)
         # rows of D(dxdt) are H_i dxdt (one device launch per kind); only D @ [dxdt, g] is needed
         rhs = self.int.hessian_rdot_mult(dxdt, np.column_stack((dxdt, g)))
         fac = self._ode_factor
@@ -777,7 +797,7 @@ class InternalPES(PES):
         g_int = self.curr.get('g')
         if g_int is None:
             g_int = np.zeros_like(dx)
-        y0 = np.hstack((self.apos.ravel(), fac.pinv_dot(np.column_stack((dx, g_int))).T.ravel()))
+        y0 = np.hstack((self._all_positions().ravel(), fac.pinv_dot(np.column_stack((dx, g_int))).T.ravel()))
         ode = LSODA(self._q_ode, 0.0, y0, t_bound=1.0, atol=1e-6)
         t0, y = 0.0, y0
         while ode.status == 'running':
@@ -790,9 +810,8 @@ class InternalPES(PES):
                 raise RuntimeError("Geometry update ODE is taking too long to converge!")
         if ode.status == 'failed':
             raise RuntimeError("Geometry update ODE failed to converge!")
-        nx = 3 * len(self.atoms)
-        y = y.reshape((3, nx))
-        self.atoms.positions = y[0].reshape((-1, 3))
+        y = y.reshape((3, self.int.ndof))
+        self.int.set_all_positions(y[0])
         B = self.int.jacobian_csr()
         return t0 * dx, t0 * (B @ y[1]), B @ y[2]
 
@@ -803,14 +822,14 @@ class InternalPES(PES):
         stagnated iteration that at least halved it and ends below 1e-6; a residual that doubles, a stagnation
         above half the initial residual or an internal coordinate turning degenerate abort.  The Newton correction
         is B^+ (target - q) with the pseudo-inverse of the CURRENT geometry (spectral factor, cached per geometry)."""
-        start = self.atoms.positions.copy()
+        start = self._all_positions()
         q0 = self.get_x()
         dq_wanted = target - q0
         g_int = self.curr.get('g')
         g_cart = self._get_factor().pinv_dot(g_int if g_int is not None else np.zeros_like(dq_wanted))
 
         def give_up():
-            self.atoms.positions = start
+            self.int.set_all_positions(start)
             return None
 
         first = previous = None
@@ -832,7 +851,7 @@ class InternalPES(PES):
             elif sweep > 3:
                 stalled = 0
             previous = rms
-            self.atoms.positions = self.atoms.positions + self._get_factor().pinv_dot(miss).reshape((-1, 3))
+            self.int.set_all_positions(self._all_positions() + self._get_factor().pinv_dot(miss).reshape((-1, 3)))
             if self.int.check_for_bad_internals() is not None:
                 return give_up()
         miss = self.wrap_dx(target - self.get_x())
@@ -867,7 +886,7 @@ class InternalPES(PES):
             dx = self._get_factor().pinv_dot(Ucons @ s)
             if np.linalg.norm(dx, ord=np.inf) > safety_limit:
                 return moved
-            self.atoms.positions = self.atoms.positions + dx.reshape(-1, 3)
+            self.int.set_all_positions(self._all_positions() + dx.reshape(-1, 3))
             moved = True
         return moved
 
@@ -935,6 +954,9 @@ class InternalPES(PES):
     # ---- calculator boundary: Cartesian gradient -> internal (:1124-1127) ---------------------------------
     def eval(self):
         f, g_cart = PES.eval(self)
+        if self.int.ndummies:
+            # the calculator knows no dummies: no force on them (`Binv[:len(g_cart)]`, :1124-1127)
+            g_cart = np.concatenate([g_cart, np.zeros(3 * self.int.ndummies)])
         return f, self._get_factor().pinvT_dot(g_cart)
 
     def get_df_pred(self, dx, g, H):                                                    # :1174-1181
@@ -953,7 +975,7 @@ class InternalPES(PES):
         B = self.curr.get('B')
         if B is None:
             B = self.int.jacobian_csr()
-        return -np.asarray((Ufree @ (Ufree.T @ g)) @ B).reshape((-1, 3))
+        return -np.asarray((Ufree @ (Ufree.T @ g)) @ B).reshape((-1, 3))[:len(self.atoms)]      # real atoms
 
     def _update(self, feval=True):
         if not PES._update(self, feval=feval):
