@@ -408,6 +408,16 @@ int sella_internals_eval(sella_ctx* ctx, int natoms, int nc, const double* pos, 
 int sella_internals_tric_eval(sella_ctx* ctx, int natoms, int nf, const int* frag_ptr, const int* frag_atoms,
                               const double* pos, const double* refpos, double* q_prev, const double* tangent, int flags,
                               double* val, double* grad, double* hvp, double* hess);
+/* The same with periodic images (the reference unwraps each fragment across the cell, internal.py:3334-3362, moving the
+ * atoms; here the atoms stay where they are): shift (frag_ptr[nf], 3) holds one Cartesian shift per CSR slot — n @ cell
+ * for the slot's integer image n — added to that slot's position wherever a position is read, before anything else:
+ * (pos + shift) - anchor, so the results equal, bit for bit, those of sella_internals_tric_eval on positions the host
+ * unwrapped itself.  The tangent takes no shift.  shift NULL: exactly sella_internals_tric_eval, which is this entry
+ * point called with NULL.                                                                                             */
+int sella_internals_tric_eval_shifted(sella_ctx* ctx, int natoms, int nf, const int* frag_ptr, const int* frag_atoms,
+                                      const double* pos, const double* shift, const double* refpos, double* q_prev,
+                                      const double* tangent, int flags, double* val, double* grad, double* hvp,
+                                      double* hess);
 
 /* ---- sparse internal-coordinate Jacobian / Hessians ------------------------------------------------- */
 /* SparseInternalJacobian, SparseInternalHessian(s) and SparseInternalHessiansSkeleton of sella/linalg.py:362-646.

@@ -150,6 +150,9 @@ SIGNATURES = {
                                      c_void_p, c_void_p]),
     'sella_internals_tric_eval': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    'sella_internals_tric_eval_shifted': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p]),
     'sella_sparse_int_create': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
     'sella_sparse_int_destroy': (c_int, [c_void_p]),
     'sella_sparse_int_set_values': (c_int, [c_void_p, c_void_p, c_void_p]),

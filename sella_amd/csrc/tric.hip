@@ -23,6 +23,13 @@
 // stride over the 3m degrees of freedom, each of which needs only per-fragment quantities.  The Hessian blocks are
 // a second launch, one thread per (a, b) pair writing all three axes, from a per-fragment state (c, P, asinc and
 // its derivatives) the first launch leaves behind.
+//
+// Periodic images (`sella_internals_tric_eval_shifted`): a fragment that crosses a cell boundary is evaluated at its
+// unwrapped geometry without moving any atom.  Each CSR slot p may carry a Cartesian shift s_p (in practice n_p @ cell
+// for an integer image n_p), added to that slot's position wherever a position is read — the anchor and the sums of R
+// in launch 1; the Hessian launch reads no position.  The shift comes first, (pos + s) - anchor, the operation order of
+// a host that unwraps the positions and calls the unshifted entry, so the two agree bit for bit.  The tangent takes no
+// shift: a lattice vector is constant, derivatives do not see it.
 #include "internal.h"
 
 namespace sella {
@@ -181,8 +188,9 @@ __device__ __forceinline__ double wave_sum(double v) {
 
 // Launch 1: one wave per fragment.  flags bit 0: value evaluation (take the branch of q_prev, store the new c).
 __global__ __launch_bounds__(256) void tric_kernel(int nf, const int* __restrict__ fptr, const int* __restrict__ fatoms,
-                                                   const double* __restrict__ pos, const double* __restrict__ ref,
-                                                   double* __restrict__ qprev, const double* __restrict__ tangent,
+                                                   const double* __restrict__ pos, const double* __restrict__ shift,
+                                                   const double* __restrict__ ref, double* __restrict__ qprev,
+                                                   const double* __restrict__ tangent,
                                                    int flags, double* __restrict__ state, double* __restrict__ val,
                                                    double* __restrict__ grad, double* __restrict__ hvp) {
     const int lane = threadIdx.x & 63;
@@ -192,16 +200,20 @@ __global__ __launch_bounds__(256) void tric_kernel(int nf, const int* __restrict
     double qp[4];
     for (int i = 0; i < 4; ++i) qp[i] = qprev[4 * f + i];     // read by every lane before lane 0 may store
     // R = sum_i (p_i - p_anchor) (x) ref_i: the anchor (first atom) drops out as the centroid does, and keeps the
-    // products free of the absolute position of the fragment
+    // products free of the absolute position of the fragment.  Shifts (periodic images) are added first.
     const int a0 = fatoms[p0];
-    const double anc[3] = {pos[3 * a0], pos[3 * a0 + 1], pos[3 * a0 + 2]};
+    double anc[3] = {pos[3 * a0], pos[3 * a0 + 1], pos[3 * a0 + 2]};
+    if (shift)
+        for (int d = 0; d < 3; ++d) anc[d] += shift[3 * (size_t)p0 + d];
     double R[9], Rt[9];
     for (int e = 0; e < 9; ++e) R[e] = Rt[e] = 0.0;
     for (int i = lane; i < m; i += 64) {
         const int at = fatoms[p0 + i];
         const double* r = ref + 3 * (size_t)(p0 + i);
         for (int d = 0; d < 3; ++d) {
-            const double x = pos[3 * (size_t)at + d] - anc[d];
+            double x = pos[3 * (size_t)at + d];
+            if (shift) x += shift[3 * (size_t)(p0 + i) + d];
+            x -= anc[d];
             for (int e = 0; e < 3; ++e) R[3 * d + e] += x * r[e];
         }
         if (tangent) {
@@ -307,9 +319,10 @@ __global__ __launch_bounds__(256) void tric_hess_kernel(int nf, const int* __res
 
 using namespace sella;
 
-extern "C" int sella_internals_tric_eval(sella_ctx* c, int natoms, int nf, const int* frag_ptr, const int* frag_atoms,
-                                         const double* pos, const double* refpos, double* q_prev, const double* tangent,
-                                         int flags, double* val, double* grad, double* hvp, double* hess) {
+extern "C" int sella_internals_tric_eval_shifted(sella_ctx* c, int natoms, int nf, const int* frag_ptr,
+                                                 const int* frag_atoms, const double* pos, const double* shift,
+                                                 const double* refpos, double* q_prev, const double* tangent, int flags,
+                                                 double* val, double* grad, double* hvp, double* hess) {
     if (!c || natoms < 0 || nf < 0 || (nf && (!frag_ptr || !frag_atoms || !pos || !refpos || !q_prev || !val || !grad)) ||
         (tangent && !hvp) || (flags & ~1)) {
         set_error("internals_tric_eval: invalid arguments");
@@ -339,15 +352,17 @@ extern "C" int sella_internals_tric_eval(sella_ctx* c, int natoms, int nf, const
         }
     }
     const size_t n3 = 3 * (size_t)natoms;
-    // one scratch block: pos | refpos | tangent | q | val | grad | hvp | state | hoff | frag_ptr | frag_atoms | hess
+    // one scratch block: pos | shift | refpos | tangent | q | val | grad | hvp | state | hoff | frag_ptr | frag_atoms |
+    // hess
     const size_t iwords = ((size_t)nf + 1 + nslot + 1) / 2 + 1;
-    const size_t words = n3 + 3 * nslot + (tangent ? n3 : 0) + 4 * (size_t)nf + 3 * (size_t)nf + 9 * nslot +
-                         (tangent ? 9 * nslot : 0) + (hess ? (size_t)TRIC_STATE * nf + nf : 0) + iwords +
-                         (hess ? (size_t)hwords : 0) + 64;
+    const size_t words = n3 + (shift ? 3 * nslot : 0) + 3 * nslot + (tangent ? n3 : 0) + 4 * (size_t)nf +
+                         3 * (size_t)nf + 9 * nslot + (tangent ? 9 * nslot : 0) +
+                         (hess ? (size_t)TRIC_STATE * nf + nf : 0) + iwords + (hess ? (size_t)hwords : 0) + 64;
     double* buf;
     SCHK(scratch_get(c, SCR_MISC0, words * sizeof(double), &buf));
     double* dpos = buf;
-    double* dref = dpos + n3;
+    double* dshift = dpos + n3;
+    double* dref = dshift + (shift ? 3 * nslot : 0);
     double* dtan = dref + 3 * nslot;
     double* dq = dtan + (tangent ? n3 : 0);
     double* dval = dq + 4 * (size_t)nf;
@@ -359,6 +374,7 @@ extern "C" int sella_internals_tric_eval(sella_ctx* c, int natoms, int nf, const
     int* datoms = dptr + nf + 1;
     double* dhess = (double*)dptr + iwords;
     SCHK(h2d_async(c, dpos, pos, n3 * sizeof(double)));
+    if (shift) SCHK(h2d_async(c, dshift, shift, 3 * nslot * sizeof(double)));
     SCHK(h2d_async(c, dref, refpos, 3 * nslot * sizeof(double)));
     if (tangent) SCHK(h2d_async(c, dtan, tangent, n3 * sizeof(double)));
     SCHK(h2d_async(c, dq, q_prev, 4 * (size_t)nf * sizeof(double)));
@@ -375,12 +391,13 @@ extern "C" int sella_internals_tric_eval(sella_ctx* c, int natoms, int nf, const
         }
         SCHK(h2d_async(c, dhoff, hoff.data(), (size_t)nf * sizeof(long)));
     }
-    // algorithmic bytes: positions and reference positions in, value + gradient (+ H t) out
-    const double bytes = 8.0 * (6.0 * nslot + (tangent ? 3.0 * nslot : 0.0) + 11.0 * nf + 9.0 * nslot * (tangent ? 2 : 1));
+    // algorithmic bytes: positions (+ shifts) and reference positions in, value + gradient (+ H t) out
+    const double bytes = 8.0 * (6.0 * nslot + (shift ? 3.0 * nslot : 0.0) + (tangent ? 3.0 * nslot : 0.0) + 11.0 * nf +
+                                9.0 * nslot * (tangent ? 2 : 1));
     prof_begin(c, PROF_OTHER, bytes, 0.0);
     SELLA_LAUNCH(c, tric_kernel, dim3((unsigned)((nf + TRIC_WAVES - 1) / TRIC_WAVES)), dim3(64 * TRIC_WAVES), 0, nf,
-                 dptr, datoms, dpos, dref, dq, tangent ? dtan : nullptr, flags, hess ? dstate : nullptr, dval, dgrad,
-                 tangent ? dhvp : nullptr);
+                 dptr, datoms, dpos, shift ? dshift : nullptr, dref, dq, tangent ? dtan : nullptr, flags,
+                 hess ? dstate : nullptr, dval, dgrad, tangent ? dhvp : nullptr);
     prof_end(c);
     HIPCHK(hipGetLastError());
     if (hess) {
@@ -398,4 +415,11 @@ extern "C" int sella_internals_tric_eval(sella_ctx* c, int natoms, int nf, const
     if (hess) SCHK(d2h_async(c, hess, dhess, (size_t)hwords * sizeof(double)));
     SCHK(stream_wait(c));
     return SELLA_OK;
+}
+
+extern "C" int sella_internals_tric_eval(sella_ctx* c, int natoms, int nf, const int* frag_ptr, const int* frag_atoms,
+                                         const double* pos, const double* refpos, double* q_prev, const double* tangent,
+                                         int flags, double* val, double* grad, double* hvp, double* hess) {
+    return sella_internals_tric_eval_shifted(c, natoms, nf, frag_ptr, frag_atoms, pos, nullptr, refpos, q_prev, tangent,
+                                             flags, val, grad, hvp, hess);
 }

@@ -518,10 +518,12 @@ class Context:
                                               ptr(hvp), ptr(hess)))
         return q, grad, hvp, hess
 
-    def tric_eval(self, frag_ptr, frag_atoms, pos, refpos, q_prev, tangent=None, hessian=False, branch=True):
-        """TRIC rotations of fragments given as CSR (`sella_internals_tric_eval`, csrc/tric.hip): values (nf, 3);
+    def tric_eval(self, frag_ptr, frag_atoms, pos, refpos, q_prev, tangent=None, hessian=False, branch=True,
+                  shift=None):
+        """TRIC rotations of fragments given as CSR (`sella_internals_tric_eval_shifted`, csrc/tric.hip): values (nf, 3);
         gradient and H t (tangent (natoms, 3)) as flat arrays holding a (3, m, 3) block per fragment at 9 frag_ptr[f];
-        Hessian as a flat array of (3, 3m, 3m) blocks.  `q_prev` (nf, 4) is updated in place when `branch`."""
+        Hessian as a flat array of (3, 3m, 3m) blocks.  `q_prev` (nf, 4) is updated in place when `branch`.  `shift`
+        (len(frag_atoms), 3): a Cartesian shift per CSR slot added to that slot's position (periodic images), or None."""
         fp = np.ascontiguousarray(frag_ptr, dtype=np.int32).ravel()
         fa = np.ascontiguousarray(frag_atoms, dtype=np.int32).ravel()
         pos = as_f64(pos)
@@ -534,14 +536,15 @@ class Context:
                 and q_prev.shape == (nf, 4)):
             raise ValueError('q_prev must be a C-contiguous float64 (nf, 4) array (it is updated in place)')
         tan = as_f64(tangent, (natoms, 3)) if tangent is not None else None
+        sh = as_f64(shift, (len(fa), 3)) if shift is not None else None
         val = np.empty((nf, 3))
         grad = np.empty(9 * fa.size)
         hvp = np.empty(9 * fa.size) if tan is not None else None
         m = np.diff(fp).astype(np.int64)
         hess = np.empty(int((27 * m * m).sum())) if hessian else None
-        check(_lib.lib().sella_internals_tric_eval(self._h, natoms, nf, ptr(fp), ptr(fa), ptr(pos), ptr(ref),
-                                                   ptr(q_prev), ptr(tan), int(bool(branch)), ptr(val), ptr(grad),
-                                                   ptr(hvp), ptr(hess)))
+        check(_lib.lib().sella_internals_tric_eval_shifted(self._h, natoms, nf, ptr(fp), ptr(fa), ptr(pos), ptr(sh),
+                                                           ptr(ref), ptr(q_prev), ptr(tan), int(bool(branch)), ptr(val),
+                                                           ptr(grad), ptr(hvp), ptr(hess)))
         return val, grad, hvp, hess
 
     def sparse_internals(self, natoms, sizes, atoms):

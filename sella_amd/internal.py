@@ -620,6 +620,11 @@ class InternalCoordinates:
     `frag_q (nfrag, 4)` (csrc/tric.hip).  Order of the coordinates, the reference's: translations, bonds, angles,
     dihedrals, rotations.
 
+    Periodic images of fragment members: `trans_ncv` and `frag_ncv` hold, parallel to `trans` and `frags`, an integer
+    cell offset n_i (m, 3) per member, and the fragment is evaluated at pos[i] + n_i @ cell (internal.py:3334-3455
+    unwraps the fragment by moving the atoms instead; here the atoms stay where they are, as they do for the `*_ncvecs`
+    of bonds, angles and dihedrals).  Zero offsets everywhere outside periodic fragments.
+
     Dummy atoms (internal.py:1214-1336): `dummies (D, 3)` are fictitious points numbered N, ..., N + D - 1 after the
     N real atoms, `dinds` (N,) names the dummy of each atom (-1: none).  Every coordinate is evaluated over
     `all_positions` = [atoms; dummies], and the Cartesian side of every Jacobian and Hessian has `ndof` = 3 (N + D)
@@ -638,7 +643,9 @@ class InternalCoordinates:
             v = np.zeros((len(a), na - 1, 3)) if ncv is None else np.asarray(ncv, dtype=np.float64).reshape(len(a), na - 1, 3)
             self.idx[name], self.ncv[name] = a, v
         self.trans = []                       # [(atom indices, dim)]
+        self.trans_ncv = []                   # per translation: integer image of each member (m, 3)
         self.frags, self.frag_ref = [], []    # rotation fragments: atom indices, centred reference positions
+        self.frag_ncv = []                    # per fragment: integer image of each member (m, 3)
         self.frag_q = np.zeros((0, 4))        # quaternion state per fragment (read and written by every evaluation)
         self.rot = []                         # [(fragment, axis)]
         self.allow_fragments = False          # guess_hessian: 0.05 Hartree for the fragment coordinates, as the reference
@@ -690,33 +697,58 @@ class InternalCoordinates:
     nint = property(lambda self: sum(len(self.idx[k]) for k in self._order) + len(self.trans) + len(self.rot))
 
     # ---- TRIC fragment coordinates (internal.py:3085-3144) -----------------------------------------------------
-    def add_translation(self, indices, dim=None):
-        """The centroid of `indices` (one atom index or several) along `dim`; all three axes when `dim` is None."""
+    @staticmethod
+    def _images(ix, ncvecs):
+        """Integer cell offsets (m, 3) of the members `ix` (zeros when None)."""
+        if ncvecs is None:
+            return np.zeros((len(ix), 3), dtype=np.int64)
+        v = np.asarray(ncvecs)
+        if v.size != 3 * len(ix) or np.any(v != np.round(v)):
+            raise ValueError(f'ncvecs must be {len(ix)} integer cell offsets (one per atom), got {v.tolist()}')
+        return np.round(v).astype(np.int64).reshape(len(ix), 3)
+
+    def _shift(self, ncv):
+        """Cartesian shifts n @ cell of integer images (m, 3); None when every image is 0 (nothing to add)."""
+        return np.asarray(ncv, dtype=np.float64) @ np.asarray(self.atoms.cell, dtype=np.float64) if np.any(ncv) else None
+
+    def add_translation(self, indices, dim=None, ncvecs=None):
+        """The centroid of `indices` (one atom index or several) along `dim`; all three axes when `dim` is None.
+        `ncvecs` (m, 3): the integer periodic image of each member, the centroid is that of pos[i] + ncvecs[i] @ cell
+        (default: zeros).  The same atoms along the same axis are the same coordinate whatever their images."""
         ix = np.atleast_1d(np.asarray(indices, dtype=np.int64)).ravel()
+        ncv = self._images(ix, ncvecs)
         if dim is None:
             for d in range(3):
-                self.add_translation(ix, d)
+                self.add_translation(ix, d, ncv)
             return
         for other, d in self.trans:
             if d == dim and len(other) == len(ix) and set(other.tolist()) == set(ix.tolist()):
                 raise DuplicateInternalError(f'translation of {ix.tolist()} along {dim} exists')
         self.trans.append((ix, int(dim)))
+        self.trans_ncv.append(ncv)
 
-    def add_rotation(self, indices, axis=None):
+    def add_rotation(self, indices, axis=None, ncvecs=None):
         """The rotation of the fragment `indices` (two atoms or more) about `axis` away from its geometry now (its
-        reference), as the exponential map of the best-aligning quaternion; all three axes when `axis` is None."""
+        reference), as the exponential map of the best-aligning quaternion; all three axes when `axis` is None.
+        `ncvecs` (m, 3): the integer periodic image of each member; the fragment is evaluated at pos[i] + ncvecs[i] @
+        cell, its reference included (default: zeros).  A fragment that exists already keeps the images it has."""
         ix = np.asarray(indices, dtype=np.int64).ravel()
         if len(ix) < 2:
             raise ValueError('a rotation coordinate needs at least 2 atoms')
+        ncv = self._images(ix, ncvecs)
         if axis is None:
             for ax in range(3):
-                self.add_rotation(ix, ax)
+                self.add_rotation(ix, ax, ncv)
             return
         frag = next((f for f, fx in enumerate(self.frags) if np.array_equal(fx, ix)), None)
         if frag is None:
             ref = np.array(self.all_positions[ix], dtype=np.float64)
+            sh = self._shift(ncv)
+            if sh is not None:
+                ref = ref + sh
             self.frags.append(ix)
             self.frag_ref.append(ref - ref.mean(axis=0))
+            self.frag_ncv.append(ncv)
             self.frag_q = np.vstack([self.frag_q, [1.0, 0.0, 0.0, 0.0]])
             frag = len(self.frags) - 1
         if (frag, int(axis)) in self.rot:
@@ -727,6 +759,15 @@ class InternalCoordinates:
         """Translation rows as (dofs (k,), weights (k,)) per row."""
         return [(3 * ix + d, np.full(len(ix), 1.0 / len(ix))) for ix, d in self.trans]
 
+    def _trans_values(self):
+        """Translation values: the mean of pos[i] + n_i @ cell along the row's axis."""
+        x = self.all_positions.ravel()
+        out = np.empty(len(self.trans))
+        for r, ((dofs, w), ncv) in enumerate(zip(self._trans_rows(), self.trans_ncv)):
+            sh = self._shift(ncv)
+            out[r] = w @ x[dofs] if sh is None else w @ (x[dofs] + sh[:, self.trans[r][1]])
+        return out
+
     def _rot_eval(self, tangent=None, hessian=False):
         """One device call for every fragment (csrc/tric.hip; updates `frag_q`): values (nrot,) and per rotation row
         its dofs (3m,), gradient (3m,), H t (3m,) when `tangent` (ndof,) is given, Hessian (3m, 3m) when `hessian`."""
@@ -735,9 +776,10 @@ class InternalCoordinates:
         sizes = np.array([len(ix) for ix in self.frags], dtype=np.int64)
         fp = np.concatenate([[0], np.cumsum(sizes)])
         tan = None if tangent is None else np.asarray(tangent, dtype=np.float64).reshape(-1, 3)
+        sh = self._shift(np.concatenate(self.frag_ncv))
         val, g, hv, H = get_context().tric_eval(fp, np.concatenate(self.frags), self.all_positions,
                                                 np.concatenate(self.frag_ref), self.frag_q, tangent=tan,
-                                                hessian=hessian)
+                                                hessian=hessian, shift=sh)
         hoff = np.concatenate([[0], np.cumsum(27 * sizes * sizes)])
         rows = []
         for f, k in self.rot:
@@ -768,8 +810,7 @@ class InternalCoordinates:
 
     def calc(self):
         """q(x) (internal.py:1735-1778), x = `all_positions`."""
-        x = self.all_positions.ravel()
-        tq = [np.array([w @ x[d] for d, w in self._trans_rows()])] if self.trans else []
+        tq = [self._trans_values()] if self.trans else []
         rq = [self._rot_eval()[0]] if self.rot else []
         return np.concatenate(tq + [evaluate_kind(k, *self._batch(k)[:2], hessian=False)[0] for k in self._order] + rq)
 
@@ -1020,7 +1061,9 @@ def _ic_copy(self):
     new = InternalCoordinates(self.atoms, self.idx['bonds'], self.idx['angles'], self.idx['dihedrals'],
                               self.ncv['bonds'], self.ncv['angles'], self.ncv['dihedrals'])
     new.trans = [(ix.copy(), d) for ix, d in self.trans]
+    new.trans_ncv = [v.copy() for v in self.trans_ncv]
     new.frags = [ix.copy() for ix in self.frags]
+    new.frag_ncv = [v.copy() for v in self.frag_ncv]
     new.frag_ref = [ref.copy() for ref in self.frag_ref]
     new.frag_q = self.frag_q.copy()
     new.rot = list(self.rot)
@@ -1111,7 +1154,9 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
       5 % and bonds BETWEEN fragments are added (`find_all_bonds`, :3366-3423; minimum-image convention);
       with `allow_fragments` the bonds of the first scale are kept as they are, and each disconnected fragment gets
       three translations (its centroid) and, with two atoms or more, three rotations (:3424-3455; the lone atoms'
-      translations first, then per fragment in order of its lowest atom index);
+      translations first, then per fragment in order of its lowest atom index).  In a periodic cell each fragment
+      member gets the integer image that makes the fragment contiguous (`_fragment_images`, :3334-3362), and the
+      fragment coordinates are evaluated there; `atoms.positions` are not changed;
     * angles: every pair of bonds at an atom whose angle lies in (atol, pi - atol), atol = 15 degrees; a (nearly)
       linear one at an atom with a third neighbour is replaced by the improper dihedral through that neighbour
       (`find_all_angles`, :3458-3573);
@@ -1243,19 +1288,49 @@ def _ic_from_atoms(cls, atoms, cons=None, scale=1.25, dihedrals=True, atol=15., 
         ic.allow_fragments = True
         labels = _fragments(natoms, bonds)
         if len(np.unique(labels)) > 1:
-            if np.any(atoms.pbc):
-                raise NotImplementedError('fragment coordinates of periodic systems (the reference unwraps each '
-                                          'fragment across the cell, internal.py:3440-3455) are not supported')
             lone = np.bincount(bonds.ravel(), minlength=natoms) == 0 if len(bonds) else np.ones(natoms, dtype=bool)
+            image = _fragment_images(natoms, bonds, bncv[:len(bonds), 0])
             for i in np.flatnonzero(lone):
                 ic.add_translation(int(i))
             for lab in np.unique(labels[~lone]):
                 group = np.flatnonzero(labels == lab)
-                # the dummies of the fragment's centres move with it (`add_dummy_to_internals`, :2708-2730)
+                # the dummies of the fragment's centres move with it (`add_dummy_to_internals`, :2708-2730), each in
+                # its centre's image
+                cen = [c for c, _, _ in dummies if labels[c] == lab]
+                ncv = np.concatenate([image[group], image[np.array(cen, dtype=np.int64)]])
                 group = np.concatenate([group, [natoms + k for k, (c, _, _) in enumerate(dummies) if labels[c] == lab]])
-                ic.add_translation(group.astype(np.int64))
-                ic.add_rotation(group.astype(np.int64))
+                ic.add_translation(group.astype(np.int64), ncvecs=ncv)
+                ic.add_rotation(group.astype(np.int64), ncvecs=ncv)
     return ic
+
+
+def _fragment_images(natoms, bonds, ncvecs):
+    """Integer periodic image (natoms, 3) of every atom that makes each fragment contiguous (`_wrap_fragment_positions`,
+    internal.py:3334-3362, without moving the atoms): a breadth-first search over the bonds from the fragment's lowest
+    atom (image 0), n_j = n_i + v for the bond i -> j with cell offset v.  A finite fragment gets the same images
+    whatever the visiting order; one bonded to its own images (a slab) keeps the first image the search reaches."""
+    image = np.zeros((natoms, 3), dtype=np.int64)
+    if not len(bonds) or not np.any(ncvecs):
+        return image
+    adj = [[] for _ in range(natoms)]
+    for (i, j), v in zip(bonds, np.round(ncvecs).astype(np.int64)):
+        adj[int(i)].append((int(j), v))
+        adj[int(j)].append((int(i), -v))
+    seen = np.zeros(natoms, dtype=bool)
+    for root in range(natoms):
+        if seen[root]:
+            continue                                   # atoms in increasing order: each fragment from its lowest atom
+        seen[root] = True
+        queue, head = [root], 0
+        while head < len(queue):
+            i = queue[head]
+            head += 1
+            for j, v in adj[i]:
+                if not seen[j]:
+                    seen[j] = True
+                    image[j] = image[i] + v
+                    queue.append(j)
+    return image
 
 
 def _dummy_site(pos, cell, c, nbrs):

@@ -6,7 +6,9 @@ trust-radius rules of `step()` (:359-434).
 `internal=True` (or an `InternalCoordinates` object) selects `InternalPES` (geodesic steps in redundant
 internal coordinates).  Options outside the saddle-point scope raise NotImplementedError:
 `optimize_cell=True` (Cell*PES).  `allow_fragments=True` with internal coordinates describes disconnected fragments by
-TRIC translations and rotations (internal.py:3366-3455) instead of bonds between them.  Linear centres with two
+TRIC translations and rotations (internal.py:3334-3455) instead of bonds between them, in periodic cells too (each
+fragment member is evaluated in the image that makes its fragment contiguous, re-derived when the internals are
+rebuilt; the atoms are not moved).  Linear centres with two
 neighbours get dummy atoms (internal.py:3480-3545); a rebuild of degraded internals places them anew.
 """
 import warnings

@@ -3,7 +3,11 @@
 formulas on the host, for two shapes: 512 three-atom fragments and 8 fragments of 200 atoms.  Times per call:
 value + gradient, value + gradient + H t, and value + gradient + Hessian blocks (API call, host copies included; the
 first launch also as the kernel time of the profiler), and the largest difference from the host restatement.
-One JSON line per (case, operation)."""
+One JSON line per (case, operation).
+
+Periodic images (`sella_internals_tric_eval_shifted`): one Cu(111) slab fragment of 256 and of 1024 atoms, every member
+with a random integer image, timed through the shifted entry against the unshifted entry on the same positions, and
+one `InternalCoordinates._rot_eval(hessian=True)` of the 256-atom fragment.  `--shifted` runs only this part."""
 import json
 import os
 import sys
@@ -134,5 +138,53 @@ def main(cases=((512, 3), (8, 200))):
     ctx.close()
 
 
+def slab_fragment(nx, ny, nz, seed=0):
+    """(positions (m, 3), cell, integer images (m, 3)) of a Cu(111) slab fragment, periodic in x and y."""
+    from sella_amd.atoms import fcc111
+    slab = fcc111('Cu', (nx, ny, nz), vacuum=7.0)
+    rng = np.random.RandomState(seed)
+    img = np.zeros((len(slab), 3), dtype=np.int64)
+    img[:, :2] = rng.randint(-1, 2, size=(len(slab), 2))
+    return slab.positions + 0.05 * rng.normal(size=slab.positions.shape), np.asarray(slab.cell), img
+
+
+def shifted(reps=20):
+    from sella_amd.atoms import Atoms
+    from sella_amd.internal import InternalCoordinates
+    ctx = Context()
+    _dev._default = ctx
+    for size in ((8, 8, 4), (16, 16, 4)):
+        pos, cell, img = slab_fragment(*size)
+        m = len(pos)
+        fp, fa = np.array([0, m]), np.arange(m)
+        sh = img @ cell
+        ref = pos + sh
+        ref = ref - ref.mean(0)
+        tan = np.random.RandomState(1).normal(size=pos.shape)
+        q0 = np.array([[1.0, 0.0, 0.0, 0.0]])
+        for op, kw in (('value+grad', {}), ('value+grad+Ht', dict(tangent=tan))):
+            row = dict(case=f'slab fragment {m} atoms', op=op)
+            for name, extra in (('unshifted', {}), ('shifted', dict(shift=sh))):
+                ctx.prof_reset()
+                ctx.prof_enable(True)
+                dt, _ = timed(lambda: ctx.tric_eval(fp, fa, pos, ref, q0.copy(), **kw, **extra), reps)
+                ctx.prof_enable(False)
+                p = ctx.prof_get(3)
+                row[f'{name}_call_us'] = round(1e6 * dt, 1)
+                row[f'{name}_kernel_us'] = round(1e3 * p['ms'] / max(1, p['launches']), 2)
+            print(json.dumps(row), flush=True)
+        if m == 256:
+            at = Atoms(['Cu'] * m, pos, cell=cell, pbc=[True, True, False])
+            ic = InternalCoordinates(at)
+            ic.add_rotation(np.arange(m), ncvecs=img)
+            dt, _ = timed(lambda: ic._rot_eval(hessian=True), 5)
+            print(json.dumps(dict(case=f'slab fragment {m} atoms', op='_rot_eval(hessian=True)',
+                                  call_ms=round(1e3 * dt, 2))), flush=True)
+    ctx.close()
+
+
 if __name__ == '__main__':
-    main()
+    if '--shifted' in sys.argv:
+        shifted()
+    else:
+        main()
