@@ -303,7 +303,8 @@ int sella_stepper_set_d1hat(sella_stepper* st, const double* d1hat, int m);
  * schedule (bisection only once niter > 4 unless newton_safe), nextafter bracket test and tolerances as the
  * reference, so the sequence of trial alphas is the reference's.
  *   cons: 0 trust region |s| (TrustRegion.cons :136-142); 1 largest per-atom displacement (RestrictedAtomicStep.cons
- *         :172-183, nout = 3 natoms); 2 largest weighted component |w_i s_i| (MaxInternalStep.cons :206-216);
+ *         :172-183: consecutive triples; when nout is not a multiple of 3 — masked cell coordinates behind the atoms — the
+ *         trailing partial group counts as padded with zeros); 2 largest weighted component |w_i s_i| (MaxInternalStep.cons :206-216);
  *         3 weighted sphere |(s + d1) * w| (IRCTrustRegion.cons :152-158).
  *   scons (nout) or NULL: the constraint-correction step added to every trial step (:35-37, :73-76);
  *   w (nout) for cons 2 / 3, d1 (nout) for cons 3;
@@ -463,6 +464,14 @@ int sella_sparse_int_jac_rmatvec(sella_sparse_int* s, const double* y, double* o
 int sella_emt_eval(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
                    const double* shifts, double rc, double acut, double cutoff, double beta,
                    double* energy, double* grad);
+/* The same evaluation plus the virial, in the same force pass (one device evaluation, one read-back).
+ * virial6 (6): W_ab = dE/d eps_ab, the derivative of the energy under the homogeneous strain x -> (I + eps) x of the
+ * positions AND the lattice translations (shifts), summed over the pairs as sum 1/2 (dE/dr / r) d_a d_b, in Voigt order
+ * (xx, yy, zz, yz, xz, xy), eV.  ASE's stress is virial6 / V (eV / Angstrom^3; a compressed crystal has negative diagonal
+ * stress).  *energy and grad are bit-for-bit those of sella_emt_eval.                                               */
+int sella_emt_eval_stress(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
+                          const double* shifts, double rc, double acut, double cutoff, double beta,
+                          double* energy, double* grad, double* virial6);
 
 /* ---- calculators that live in the library, and the finite-difference Hessian on top of one ----------------- */
 /* sella/peswrapper.py:413-418 evaluates energy and forces through `atoms.calc`; for a calculator implemented HERE that

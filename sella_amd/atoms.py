@@ -2,7 +2,8 @@
 image; when `ase` imports, its own classes are used instead and these are bypassed).
 
   Atoms       positions / cell / pbc / calc, get_potential_energy(), get_forces()  — exactly the
-              attributes `PES` reads (sella/peswrapper.py:294-303,332-338,413-418)
+              attributes `PES` reads (sella/peswrapper.py:294-303,332-338,413-418) — and get_cell(), set_cell(),
+              get_volume(), get_stress(), get_pbc(), the subset of ASE's interface `CellCartesianPES` uses
   Optimizer   the run()/irun()/log()/converged() loop `Sella` inherits from
               ase.optimize.optimize.Optimizer (sella/optimize/optimize.py:10,177)
   calculators on the far side of the calculator boundary, for tests and benchmarks:
@@ -85,6 +86,28 @@ class Atoms:
     def get_potential_energy(self):
         return float(self.calc.get_potential_energy(self))
 
+    # ---- the cell (ase.Atoms.get_cell / set_cell / get_volume / get_pbc; get_cell hands out a plain array) ----------
+    def get_cell(self):
+        return self.cell.copy()
+
+    def set_cell(self, cell, scale_atoms=False):
+        """New lattice vectors (rows); with scale_atoms the positions keep their fractional coordinates."""
+        cell = np.array(cell, dtype=np.float64).reshape(3, 3)
+        if scale_atoms:
+            self.positions = self.positions @ np.linalg.solve(self.cell, cell)
+        self.cell = cell
+
+    def get_volume(self):
+        return float(abs(np.linalg.det(self.cell)))
+
+    def get_pbc(self):
+        return self.pbc.copy()
+
+    def get_stress(self):
+        """Stress in Voigt order (xx, yy, zz, yz, xz, xy), eV / Angstrom^3, from the calculator (ASE's convention:
+        V sigma_ab = dE / d eps_ab under a homogeneous strain, negative diagonal for a compressed crystal)."""
+        return np.asarray(self.calc.get_stress(self), dtype=np.float64).reshape(6)
+
     def get_forces(self):
         return np.asarray(self.calc.get_forces(self), dtype=np.float64).reshape((-1, 3))
 
@@ -158,7 +181,7 @@ class XYZTrajectory:
         cell = np.asarray(at.cell, dtype=float).ravel()
         calc = at.calc
         res = getattr(calc, '_res', None)
-        have = res is not None and getattr(calc, '_key', None) == at.positions.tobytes()
+        have = res is not None and getattr(calc, '_key', None) == cache_key(at)
         head = 'Lattice="%s" Properties=species:S:1:pos:R:3%s pbc="%s"' % (
             ' '.join('%.10f' % v for v in cell), ':forces:R:3' if have else '',
             ' '.join('T' if b else 'F' for b in at.pbc))
@@ -179,12 +202,40 @@ class XYZTrajectory:
             self.f.close()
 
 
+def cache_key(atoms):
+    """What a calculator's results are cached under: the positions and the cell (a probe of the cell alone is a new
+    geometry)."""
+    return np.ascontiguousarray(atoms.positions).tobytes() + np.asarray(atoms.cell, dtype=np.float64).tobytes()
+
+
+def voigt_to_matrix(v):
+    """3 x 3 symmetric tensor of a Voigt 6-vector (xx, yy, zz, yz, xz, xy)."""
+    xx, yy, zz, yz, xz, xy = v
+    return np.array([[xx, xy, xz], [xy, yy, yz], [xz, yz, zz]], dtype=np.float64)
+
+
+def supports_stress(calc):
+    """Whether `calc` can produce a stress tensor: a calculator of this module that implements the virial, or a foreign
+    (ASE) calculator with `get_stress` that lists 'stress' among its implemented properties (if it lists any)."""
+    if calc is None:
+        return False
+    if isinstance(calc, Calculator):
+        return type(calc).energy_gradient_virial is not Calculator.energy_gradient_virial
+    if not callable(getattr(calc, 'get_stress', None)):
+        return False
+    props = getattr(calc, 'implemented_properties', None)
+    return props is None or 'stress' in props
+
+
 class Calculator:
-    """energy_and_gradient(positions (N,3)) -> (E, dE/dx (N,3)); results cached per geometry."""
+    """energy_and_gradient(positions (N,3)) -> (E, dE/dx (N,3)); results cached per geometry (positions and cell).
+    A calculator that also has the virial implements energy_gradient_virial(positions) -> (E, dE/dx, W (6,)), W the
+    derivative of E under a homogeneous strain in Voigt order; get_stress() is then W / V from the same evaluation."""
 
     def __init__(self):
         self._key = None
         self._res = None
+        self._virial = None
         self._ncalls = 0
 
     def _library_calls(self):
@@ -206,11 +257,20 @@ class Calculator:
     def device_calculator(self):
         return None
 
-    def _get(self, atoms):
-        key = atoms.positions.tobytes()
-        if key != self._key:
+    def energy_gradient_virial(self, pos):
+        raise NotImplementedError(f'{type(self).__name__} has no stress tensor')
+
+    def _get(self, atoms, stress=False):
+        """(E, dE/dx) of the geometry of `atoms`; with `stress`, the virial is cached alongside them from the same
+        evaluation (energy and forces cached without it cost one more)."""
+        key = cache_key(atoms)
+        if key != self._key or (stress and self._virial is None):
             self._ncalls += 1
-            self._res = self.energy_and_gradient(atoms.positions)
+            if stress:
+                e, g, w = self.energy_gradient_virial(atoms.positions)
+                self._res, self._virial = (e, g), np.asarray(w, dtype=np.float64).copy()
+            else:
+                self._res, self._virial = self.energy_and_gradient(atoms.positions), None
             self._key = key
         return self._res
 
@@ -219,6 +279,14 @@ class Calculator:
 
     def get_forces(self, atoms):
         return -self._get(atoms)[1]
+
+    def get_stress(self, atoms):
+        """Stress (Voigt order xx, yy, zz, yz, xz, xy; eV / Angstrom^3) = virial / V."""
+        self._get(atoms, stress=True)
+        volume = abs(np.linalg.det(np.asarray(atoms.cell, dtype=np.float64)))
+        if volume == 0.0:
+            raise ValueError('stress needs a cell with a non-zero volume')
+        return self._virial / volume
 
 
 class QuadraticCubicModel(Calculator):
@@ -286,11 +354,18 @@ class PeriodicMorse(Calculator):
         self.D, self.a, self.r0, self.rcut = D, a, r0, rcut
         self.cell, self.pbc = None, None
 
-    def _get(self, atoms):
+    def _get(self, atoms, stress=False):
         self.cell, self.pbc = np.asarray(atoms.cell, dtype=float), np.asarray(atoms.pbc, dtype=bool)
-        return super()._get(atoms)
+        return super()._get(atoms, stress)
 
     def energy_and_gradient(self, pos):
+        return self._evaluate(pos, False)
+
+    def energy_gradient_virial(self, pos):
+        """Energy, gradient and virial sum_pairs (dE/dr / r) d (x) d over the minimum-image pairs (Voigt order)."""
+        return self._evaluate(pos, True)
+
+    def _evaluate(self, pos, virial):
         n = len(pos)
         iu = np.triu_indices(n, 1)
         d = pos[iu[0]] - pos[iu[1]]
@@ -316,7 +391,10 @@ class PeriodicMorse(Calculator):
         u = d / rr[:, None]
         np.add.at(g, i0, de[:, None] * u)
         np.add.at(g, i1, -de[:, None] * u)
-        return e, g
+        if not virial:
+            return e, g
+        W = np.einsum('p,pa,pb->ab', de / rr, d, d)
+        return e, g, np.array([W[0, 0], W[1, 1], W[2, 2], W[1, 2], W[0, 2], W[0, 1]])
 
 
 class EMT(Calculator):
@@ -325,8 +403,9 @@ class EMT(Calculator):
     device (csrc/emt.hip: all-pairs density / cohesive / force kernels, deterministic in-block reductions).
     ASE is not installable in the build image, so this restates the published algorithm: **unpinned** against
     ASE; checked against the NumPy restatement in oracle/ and finite differences of its own energy.  Periodic
-    directions are handled by an explicit sum over the 3^d neighbouring images, so the cell only has to be
-    wider than the cutoff (~5.9 A for Cu), not twice it."""
+    directions are handled by an explicit sum over the periodic images: ceil(cutoff / height) of them on either side
+    along each periodic direction (one while the cell is at least a cutoff, ~5.3 A for Cu, wide), 127 images at most.
+    get_stress() takes energy, forces and the virial from one device evaluation (`sella_emt_eval_stress`)."""
     #              E0     s0    V0     eta2   kappa  lambda n0        (eV, bohr, eV, 1/bohr, 1/bohr, 1/bohr, 1/bohr^3)
     _PAR = dict(Al=(-3.28, 3.00, 1.493, 1.240, 2.000, 1.169, 0.00700), Cu=(-3.51, 2.67, 2.476, 1.652, 2.740, 1.906, 0.00910),
                 Ag=(-2.96, 3.01, 2.132, 1.652, 2.790, 1.892, 0.00547), Au=(-3.80, 3.00, 2.321, 1.674, 2.873, 2.182, 0.00703),
@@ -339,12 +418,12 @@ class EMT(Calculator):
         super().__init__()
         self._setup = None
 
-    def _get(self, atoms):
+    def _get(self, atoms, stress=False):
         key = (tuple(atoms.symbols), np.asarray(atoms.cell, dtype=float).tobytes(), tuple(atoms.pbc))
         if self._setup is None or self._setup[0] != key:
             self._setup = (key, self._initialize(atoms))
             self._key = None                       # results cached for the old cell / species are stale
-        return super()._get(atoms)
+        return super()._get(atoms, stress)
 
     def _initialize(self, atoms):
         b, beta = self._BOHR, self._BETA
@@ -368,17 +447,45 @@ class EMT(Calculator):
             p['gamma1'], p['gamma2'] = g1, g2
         table = np.array([[par[s][name] for s in atoms.symbols]
                           for name in ('E0', 's0', 'V0', 'eta2', 'kappa', 'lam', 'n0', 'gamma1', 'gamma2')])
-        cell = np.asarray(atoms.cell, dtype=float)
+        cutoff = rc + 0.5
+        shifts = self.image_shifts(atoms.cell, atoms.pbc, cutoff)
+        return dict(par=np.ascontiguousarray(table), rc=rc, acut=acut, cutoff=cutoff, shifts=shifts)
+
+    _MAX_IMAGES = 127                  # the packing limit of the device's neighbour lists (csrc/emt.hip, emt_pack)
+
+    @classmethod
+    def image_shifts(cls, cell, pbc, cutoff):
+        """Lattice translations of the periodic images to sum over: k = -m_d .. m_d along each periodic direction d,
+        m_d = ceil(cutoff / height_d) (height_d: distance between the lattice planes the other periodic vectors span),
+        nested in the order x, y, z.  A cell at least one cutoff wide in every periodic direction gives the 3^d list."""
+        cell = np.asarray(cell, dtype=float)
+        per = [d for d in range(3) if pbc[d]]
+        m = {}
+        if per:
+            dual = np.linalg.pinv(cell[per])                     # columns: dual vectors within the periodic lattice
+            for k, d in enumerate(per):
+                norm = np.linalg.norm(dual[:, k])
+                if not np.isfinite(norm) or norm == 0.0:
+                    raise ValueError('EMT: degenerate periodic cell')
+                m[d] = int(np.ceil(cutoff * norm))
+        count = int(np.prod([2 * m[d] + 1 for d in per])) if per else 1
+        if count > cls._MAX_IMAGES:
+            raise ValueError(f'EMT: the cell needs {count} periodic images within the cutoff ({cutoff:.3f} A), more than '
+                             f'{cls._MAX_IMAGES}')
         shifts = [np.zeros(3)]
-        for d in range(3):
-            if atoms.pbc[d]:
-                shifts = [sft + k * cell[d] for sft in shifts for k in (-1, 0, 1)]
-        return dict(par=np.ascontiguousarray(table), rc=rc, acut=acut, cutoff=rc + 0.5, shifts=np.array(shifts))
+        for d in per:
+            shifts = [sft + k * cell[d] for sft in shifts for k in range(-m[d], m[d] + 1)]
+        return np.array(shifts)
 
     def energy_and_gradient(self, pos):
         from .device import get_context
         S = self._setup[1]
         return get_context().emt_eval(pos, S['par'], S['shifts'], S['rc'], S['acut'], S['cutoff'], self._BETA)
+
+    def energy_gradient_virial(self, pos):
+        from .device import get_context
+        S = self._setup[1]
+        return get_context().emt_eval_stress(pos, S['par'], S['shifts'], S['rc'], S['acut'], S['cutoff'], self._BETA)
 
     library_form = True
 

@@ -157,7 +157,11 @@ __device__ __forceinline__ void emt_density_vb(const VB vb, EmtArgs a) {
 }
 __global__ __launch_bounds__(256) void emt_density_kernel(EmtArgs a) { emt_density_vb(vb_hw(), a); }
 
-__device__ __forceinline__ void emt_force_vb(const VB vb, EmtArgs a) {
+// VIRIAL: every thread also accumulates the symmetric virial of the pairs it visits, 1/2 (dE/dr / r) d (x) d per pair
+// (each unordered pair is gathered once from either end), and the block writes the six components (xx, yy, zz, yz, xz,
+// xy) of its atom to grad + 3 n + 6 i.  VIRIAL = false is the force pass alone.
+template <bool VIRIAL>
+__device__ __forceinline__ void emt_force_body(const VB vb, EmtArgs a) {
     __shared__ double red[4];
     __shared__ int hits[256][EMT_HCAP + 1];
     __shared__ EmtStage stage;
@@ -167,6 +171,7 @@ __device__ __forceinline__ void emt_force_vb(const VB vb, EmtArgs a) {
     const double n0i = a.p.n0[i], g1i = a.p.gamma1[i], g2i = a.p.gamma2[i], V0i = a.p.V0[i];
     const double eta2i = a.p.eta2[i], kapi = a.p.kappa[i], s0i = a.p.s0[i], dEi = a.dEdsig[i];
     double gx = 0.0, gy = 0.0, gz = 0.0;
+    double wxx = 0.0, wyy = 0.0, wzz = 0.0, wyz = 0.0, wxz = 0.0, wxy = 0.0;
     auto heavy = [&](int t) {
         const int j = t & 0xffffff, s = t >> 24;
         const double dx = a.pos[3 * j] + a.shifts[3 * s] - xi;
@@ -191,6 +196,11 @@ __device__ __forceinline__ void emt_force_vb(const VB vb, EmtArgs a) {
             gx -= f * dx;
             gy -= f * dy;
             gz -= f * dz;
+            if constexpr (VIRIAL) {
+                const double h = 0.5 * f;
+                wxx += h * (dx * dx); wyy += h * (dy * dy); wzz += h * (dz * dz);
+                wyz += h * (dy * dz); wxz += h * (dx * dz); wxy += h * (dx * dy);
+            }
         }
     };
     // neighbours from the density kernel's lists; the sweep again only if some thread's list overflowed there
@@ -213,8 +223,23 @@ __device__ __forceinline__ void emt_force_vb(const VB vb, EmtArgs a) {
         a.grad[3 * i + 1] = gy;
         a.grad[3 * i + 2] = gz;
     }
+    if constexpr (VIRIAL) {
+        wxx = block_sum(wxx, red);
+        wyy = block_sum(wyy, red);
+        wzz = block_sum(wzz, red);
+        wyz = block_sum(wyz, red);
+        wxz = block_sum(wxz, red);
+        wxy = block_sum(wxy, red);
+        if (threadIdx.x == 0) {
+            double* w = a.grad + 3 * (size_t)a.n + 6 * (size_t)i;
+            w[0] = wxx; w[1] = wyy; w[2] = wzz; w[3] = wyz; w[4] = wxz; w[5] = wxy;
+        }
+    }
 }
+__device__ __forceinline__ void emt_force_vb(const VB vb, EmtArgs a) { emt_force_body<false>(vb, a); }
+__device__ __forceinline__ void emt_force_virial_vb(const VB vb, EmtArgs a) { emt_force_body<true>(vb, a); }
 __global__ __launch_bounds__(256) void emt_force_kernel(EmtArgs a) { emt_force_vb(vb_hw(), a); }
+__global__ __launch_bounds__(256) void emt_force_virial_kernel(EmtArgs a) { emt_force_virial_vb(vb_hw(), a); }
 
 }  // namespace
 }  // namespace sella
@@ -222,32 +247,46 @@ __global__ __launch_bounds__(256) void emt_force_kernel(EmtArgs a) { emt_force_v
 using namespace sella;
 
 // dconst != nullptr: the parameter table and the shift vectors are resident already (9 n + 3 nshift doubles, uploaded by
-// the caller once: sella_calc_emt_create) — a force call is then one upload (positions), two kernels, one read-back
+// the caller once: sella_calc_emt_create) — a force call is then one upload (positions), two kernels, one read-back.
+// virial6 != nullptr: the force pass also reduces the per-atom virials (emt_force_virial_kernel), summed here in index
+// order like the energies; the read-back is then 10 n doubles instead of 4 n.
 int sella::emt_eval_resident(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
                              const double* dconst, double rc, double acut, double cutoff, double beta, double* energy,
-                             double* grad) {
+                             double* grad, double* virial6) {
     double *dea, *dgr;
-    SCHK(emt_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, &dea, &dgr));
-    // per-atom energies and the gradient sit back to back: one read-back
+    SCHK(emt_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, &dea, &dgr, virial6 != nullptr));
+    // per-atom energies, the gradient and (if asked for) the per-atom virials sit back to back: one read-back
+    const size_t nout = (size_t)(virial6 ? 10 : 4) * n;
     std::vector<double>& out = c->hbuf_b;
-    out.resize((size_t)4 * n);
-    SCHK(d2h_async(c, out.data(), dea, (size_t)4 * n * sizeof(double)));
+    out.resize(nout);
+    SCHK(d2h_async(c, out.data(), dea, nout * sizeof(double)));
     SCHK(stream_wait(c));
     double e = 0.0;
     for (int i = 0; i < n; ++i) e += out[i];
     *energy = e;
     for (size_t i = 0; i < (size_t)3 * n; ++i) grad[i] = out[(size_t)n + i];
+    if (virial6) {
+        const double* w = out.data() + (size_t)4 * n;
+        for (int k = 0; k < 6; ++k) {
+            double v = 0.0;
+            for (int i = 0; i < n; ++i) v += w[6 * (size_t)i + k];
+            virial6[k] = v;
+        }
+    }
     return SELLA_OK;
 }
 
 // the same up to the kernels: positions uploaded, two launches queued, nothing waited for.  *eatom (n per-atom
-// energies, summed by the caller in index order) and *grad (3 n, directly behind) stay valid until scratch slot
-// SCR_MISC0 is used again.
+// energies, summed by the caller in index order) and *grad (3 n, directly behind; with `virial`, the n x 6 per-atom
+// virials directly behind that) stay valid until scratch slot SCR_MISC0 is used again.
 int sella::emt_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
-                     const double* dconst, double rc, double acut, double cutoff, double beta, double** eatom, double** grad) {
+                     const double* dconst, double rc, double acut, double cutoff, double beta, double** eatom, double** grad,
+                     bool virial) {
     if (n >= (1 << 24) || nshift > 127) { set_error("emt: at most 2^24 atoms and 127 periodic images"); return SELLA_E_INVALID; }
+    const size_t nvir = virial ? (size_t)6 * n : 0;
     const size_t nbr_words = ((size_t)n * 256 * (EMT_HCAP + 1) + 1) / 2;
-    const size_t words = (size_t)3 * n + (size_t)9 * n + (size_t)3 * nshift + (size_t)4 * n + (size_t)3 * n + 64 + nbr_words;
+    const size_t words = (size_t)3 * n + (size_t)9 * n + (size_t)3 * nshift + (size_t)4 * n + (size_t)3 * n + nvir + 64
+                         + nbr_words;
     double* buf;
     SCHK(scratch_get(c, SCR_MISC0, words * sizeof(double), &buf));
     double* dpos = buf;
@@ -274,9 +313,12 @@ int sella::emt_queue(sella_ctx* c, int n, const double* pos, const double* par, 
     a.p.gamma1 = dpar + 7 * (size_t)n; a.p.gamma2 = dpar + 8 * (size_t)n;
     a.rc = rc; a.acut = acut; a.cutoff = cutoff; a.beta = beta;
     a.sigma1 = dsig; a.epair = dep; a.dEdsig = dde; a.eatom = dea; a.grad = dgr;
-    a.nbr = reinterpret_cast<int*>(dgr + 3 * (size_t)n + 32);
+    a.nbr = reinterpret_cast<int*>(dgr + 3 * (size_t)n + nvir + 32);
     SELLA_LAUNCHB(c, emt_density_kernel, emt_density_vb, 256, dim3(n), dim3(256), 0, a);
-    SELLA_LAUNCHB(c, emt_force_kernel, emt_force_vb, 256, dim3(n), dim3(256), 0, a);
+    if (virial)
+        SELLA_LAUNCHB(c, emt_force_virial_kernel, emt_force_virial_vb, 256, dim3(n), dim3(256), 0, a);
+    else
+        SELLA_LAUNCHB(c, emt_force_kernel, emt_force_vb, 256, dim3(n), dim3(256), 0, a);
     HIPCHK(hipGetLastError());
     *eatom = dea;
     *grad = dgr;
@@ -291,4 +333,14 @@ extern "C" int sella_emt_eval(sella_ctx* c, int n, const double* pos, const doub
         return SELLA_E_INVALID;
     }
     return emt_eval_resident(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta, energy, grad);
+}
+
+extern "C" int sella_emt_eval_stress(sella_ctx* c, int n, const double* pos, const double* par /* 9 x n */, int nshift,
+                                     const double* shifts, double rc, double acut, double cutoff, double beta,
+                                     double* energy, double* grad, double* virial6) {
+    if (!c || n <= 0 || !pos || !par || nshift <= 0 || !shifts || !energy || !grad || !virial6) {
+        set_error("emt_eval_stress: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    return emt_eval_resident(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta, energy, grad, virial6);
 }

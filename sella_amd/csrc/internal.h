@@ -428,11 +428,13 @@ int lr_lowrank_update(sella_ctx* c, int n, int* r_io, double* mu, double lam0, M
 // too when not null.  No wait (sella_sparse_int_eval writes straight into the buffers of its topology).
 int internals_queue(sella_ctx* c, int natoms, int nc, const double* dpos, const double* dtv, double* dq, double* dgrad,
                     double* dhess);
-// emt.hip: sella_emt_eval with the parameter table and shift vectors optionally resident (dconst: 9 n + 3 nshift doubles)
+// emt.hip: sella_emt_eval with the parameter table and shift vectors optionally resident (dconst: 9 n + 3 nshift doubles);
+// virial6 != nullptr: the six summed virial components too (sella_emt_eval_stress)
 int emt_eval_resident(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
-                      const double* dconst, double rc, double acut, double cutoff, double beta, double* energy, double* grad);
+                      const double* dconst, double rc, double acut, double cutoff, double beta, double* energy, double* grad,
+                      double* virial6 = nullptr);
 int emt_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts, const double* dconst,
-              double rc, double acut, double cutoff, double beta, double** eatom, double** grad);
+              double rc, double acut, double cutoff, double beta, double** eatom, double** grad, bool virial = false);
 // calc.hip: a force call of a library calculator in two halves, so that what consumes the gradient can be queued behind
 // it without a wait in between.  calc_queue: x (host) uploaded, kernels queued; *g_dev = gradient on the device (n),
 // *aux_dev / *naux = what the energy is assembled from.  calc_finish: energy from the read-back aux values, after the wait.

@@ -472,10 +472,13 @@ __device__ __forceinline__ void rs_measure_vb(const VB vb, int cons, int nout, c
         acc = wave_sum64(acc);
     } else {
         if (cons == 1) {
-            for (int at = tid; at < nout / 3; at += 256) {
+            // groups of three; a trailing partial group (cell coordinates under a mask) counts as padded with zeros
+            for (int at = tid; at < (nout + 2) / 3; at += 256) {
                 double n2 = 0.0;
 #pragma unroll
-                for (int q = 0; q < 3; ++q) { const double st = stot(3 * at + q); n2 += st * st; }
+                for (int q = 0; q < 3; ++q) {
+                    if (3 * at + q < nout) { const double st = stot(3 * at + q); n2 += st * st; }
+                }
                 acc = fmax(acc, sqrt(n2));
             }
         } else {
@@ -547,12 +550,13 @@ __device__ __forceinline__ void rs_cons_vb(const VB vb, int cons, int nout, cons
     double best = -1.0, bd = 0.0;
     int bi = 0x7fffffff;
     if (cons == 1) {
-        const int natoms = nout / 3;
+        const int natoms = (nout + 2) / 3;                     // a trailing partial group: padded with zeros
         for (int a = tid; a < natoms; a += 1024) {
             double n2 = 0.0, dd = 0.0;
 #pragma unroll
             for (int q = 0; q < 3; ++q) {
                 const int i = 3 * a + q;
+                if (i >= nout) continue;
                 const double st = s[i] + (scons ? scons[i] : 0.0);
                 stot[i] = st;
                 n2 += st * st;
@@ -685,7 +689,6 @@ extern "C" int sella_restricted_step(sella_stepper* st, int cons, double delta, 
                                                        // m < nfam for a structured eigendecomposition, sella_stepper_create_lr)
     if (sel && nfull < nfam) { set_error("restricted_step: a selection needs nfull >= the family's dimension"); return SELLA_E_INVALID; }
     const int nout = sel ? nfull : nfam;               // dimension of the step handed back
-    if (cons == 1 && nout % 3 != 0) { set_error("restricted_step: per-atom measure needs 3 N components"); return SELLA_E_INVALID; }
     const int ldx = round_up(m, 8), ldy = round_up(std::max(nout, nfam), 8);
     double *dx, *dy, *dv;
     SCHK(scratch_get(c, SCR_STEP0, (size_t)2 * std::max(ldx, ldy) * sizeof(double), &dx));

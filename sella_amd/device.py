@@ -565,6 +565,20 @@ class Context:
                                         float(acut), float(cutoff), float(beta), byref(e), ptr(grad)))
         return e.value, grad
 
+    def emt_eval_stress(self, pos, par, shifts, rc, acut, cutoff, beta):
+        """(energy, gradient (n, 3), virial (6,)) of the EMT potential from one device evaluation: energy and gradient
+        as `emt_eval`'s, virial = dE/d(strain) in Voigt order (xx, yy, zz, yz, xz, xy), eV (stress = virial / V)."""
+        pos = as_f64(pos)
+        par = as_f64(par)
+        shifts = as_f64(shifts)
+        n = pos.shape[0]
+        e = c_double(0.0)
+        grad = np.empty((n, 3))
+        virial = np.empty(6)
+        check(_lib.lib().sella_emt_eval_stress(self._h, n, ptr(pos), ptr(par), shifts.shape[0], ptr(shifts), float(rc),
+                                               float(acut), float(cutoff), float(beta), byref(e), ptr(grad), ptr(virial)))
+        return e.value, grad, virial
+
     # ---- profiling ---------------------------------------------------------------------------
     def prof_enable(self, on=True):
         check(_lib.lib().sella_prof_enable(self._h, int(bool(on))))

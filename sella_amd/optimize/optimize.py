@@ -4,22 +4,31 @@ ASE `Optimizer` (or the built-in equivalent when ASE is absent), the diagonalisa
 trust-radius rules of `step()` (:359-434).
 
 `internal=True` (or an `InternalCoordinates` object) selects `InternalPES` (geodesic steps in redundant
-internal coordinates).  Options outside the saddle-point scope raise NotImplementedError:
-`optimize_cell=True` (Cell*PES).  `allow_fragments=True` with internal coordinates describes disconnected fragments by
-TRIC translations and rotations (internal.py:3334-3455) instead of bonds between them, in periodic cells too (each
-fragment member is evaluated in the image that makes its fragment contiguous, re-derived when the internals are
-rebuilt; the atoms are not moved).  Linear centres with two
-neighbours get dummy atoms (internal.py:3480-3545); a rebuild of degraded internals places them anew.
+internal coordinates).  `optimize_cell=True` (minima of periodic systems, Cartesian coordinates) relaxes the positions
+and the unit cell together through `CellCartesianPES` (optimize.py:70-140, 289-300 of the reference), with the
+keywords cell_mask, exp_cell_factor, scalar_pressure, smax, refine_initial_hessian and save_hessian; it needs a
+calculator with a stress tensor.  Cell optimisation in internal coordinates (CellInternalPES) and Niggli reduction
+are not built and raise NotImplementedError.  `allow_fragments=True` with internal coordinates
+describes disconnected fragments by TRIC translations and rotations (internal.py:3334-3455) instead of bonds between
+them, in periodic cells too (each fragment member is evaluated in the image that makes its fragment contiguous,
+re-derived when the internals are rebuilt; the atoms are not moved).  Linear centres with two neighbours get dummy
+atoms (internal.py:3480-3545); a rebuild of degraded internals places them anew.
 """
 import warnings
 from time import localtime, strftime
 
 import numpy as np
 
-from ..atoms import Optimizer
+from ..atoms import Optimizer, supports_stress
 from ..internal import Constraints
-from ..peswrapper import PES
+from ..peswrapper import PES, CellCartesianPES
 from .restricted_step import get_restricted_step
+
+
+class CellOptimizationError(ValueError, NotImplementedError):
+    """`optimize_cell=True` where the reference refuses it with a ValueError — a saddle search (order != 0) or a system
+    without a periodic direction; a NotImplementedError too, like the other options this package does not cover."""
+
 
 _default_kwargs = dict(
     minimum=dict(delta0=1e-1, sigma_inc=1.15, sigma_dec=0.90, rho_inc=1.035, rho_dec=100,
@@ -40,23 +49,26 @@ class Sella(Optimizer):
                  refine_initial_hessian=False, save_hessian=None, exact_geodesic=None, **kwargs):
         # keyword set of the reference constructor (optimize.py:42-80).  The cell keywords (cell_mask,
         # exp_cell_factor, scalar_pressure, smax, niggli, refine_initial_hessian, save_hessian) only act with
-        # optimize_cell=True there and are accepted and ignored here as there; the two that would change the
-        # saddle-point path are refused.
+        # optimize_cell=True, there as here.
         if optimize_cell:
-            raise NotImplementedError('optimize_cell requires order=0 and is outside the saddle-point scope')
+            self._check_cell_run(atoms, order, internal, niggli)
+        self.optimize_cell = bool(optimize_cell)
+        self.smax = smax
+        self.delta_cell = None
+        cell_kw = dict(cell_mask=cell_mask, exp_cell_factor=exp_cell_factor, scalar_pressure=scalar_pressure,
+                       refine_initial_hessian=refine_initial_hessian, save_hessian=save_hessian)
         # allow_fragments: disconnected fragments get TRIC translations and rotations instead of artificial bonds
         # between them (internal coordinates only; accepted and ignored in Cartesian coordinates, as the reference)
         self.allow_fragments = bool(allow_fragments)
         # the reference integrates the exact geodesic unless told otherwise (optimize.py:125)
         self.exact_geodesic = exact_geodesic is None or bool(exact_geodesic)
-        self.optimize_cell = False
         self.user_internal, self.peskwargs = internal, dict(kwargs)
         self._user_constraints = constraints
         # what `LibrarySearch` would be built from (`run` hands the whole search to the library when it is covered)
         self._lib, self._lib_authoritative = None, False
         self._lib_kw = None
-        if (not internal and restart is None and v0 is None and hessian_function is None and trajectory is None
-                and logfile is None and master is None and not (set(kwargs) - {'proj_trans', 'proj_rot'})):
+        if (not internal and not optimize_cell and restart is None and v0 is None and hessian_function is None
+                and trajectory is None and logfile is None and master is None and not (set(kwargs) - {'proj_trans', 'proj_rot'})):
             self._lib_kw = dict(order=order, eta=eta, gamma=gamma, delta0=delta0, sigma_inc=sigma_inc, sigma_dec=sigma_dec,
                                 rho_inc=rho_inc, rho_dec=rho_dec, rs=rs, method=method, eig=eig, threepoint=threepoint,
                                 nsteps_per_diag=nsteps_per_diag, diag_every_n=diag_every_n, constraints=constraints,
@@ -65,7 +77,8 @@ class Sella(Optimizer):
         if own_traj:                                                              # :144-150
             from ..peswrapper import open_trajectory
             trajectory = open_trajectory(trajectory, atoms, append=append_trajectory)
-        self.initialize_pes(atoms, trajectory, order, eta, constraints, v0, internal, hessian_function, **kwargs)
+        self.initialize_pes(atoms, trajectory, order, eta, constraints, v0, internal, hessian_function,
+                            **(dict(kwargs, **cell_kw) if optimize_cell else kwargs))
         Optimizer.__init__(self, atoms, restart=restart, logfile=logfile, trajectory=None, master=master)
         if own_traj:
             self.closelater(trajectory)
@@ -90,6 +103,8 @@ class Sella(Optimizer):
         self.delta = chosen['delta0'] * (self.pes.get_Ufree().shape[1] if per_dof else 1)
         self.delta_min = eta
         self.rho, self.xi = 1., 1.
+        if self.optimize_cell:
+            self.delta_cell = chosen['delta0']            # kept and logged (strust) like the reference's (:187)
 
         # curvature schedule (:187-197)
         self.diagkwargs = {'gamma': gamma, 'threepoint': threepoint}
@@ -211,6 +226,22 @@ class Sella(Optimizer):
             self.pairs_adopted = pending[0].shape[1]
         ls.close()
 
+    @staticmethod
+    def _check_cell_run(atoms, order, internal, niggli):
+        """The refusals of optimize_cell=True (optimize.py:128-140 of the reference, and what is not built here)."""
+        if order != 0:
+            raise CellOptimizationError(f'cell optimization is only supported for minima (order=0), got order={order}')
+        if not np.any(atoms.pbc):
+            raise CellOptimizationError('cell optimization requires periodic boundary conditions')
+        if internal:
+            raise NotImplementedError('optimize_cell=True with internal coordinates (CellInternalPES) is not implemented')
+        if niggli:
+            raise NotImplementedError('niggli=True (Niggli reduction of the cell) is not implemented')
+        calc = getattr(atoms, 'calc', None)
+        if not supports_stress(calc):
+            raise NotImplementedError(f'optimize_cell=True needs a stress tensor, and the calculator '
+                                      f'{type(calc).__name__} has none')
+
     def initialize_pes(self, atoms, trajectory=None, order=1, eta=1e-4, constraints=None, v0=None,
                        internal=False, hessian_function=None, **kwargs):
         if internal:                                                              # :237-285
@@ -237,7 +268,8 @@ class Sella(Optimizer):
         if constraints is None:
             constraints = Constraints(atoms)
         self.constraints = constraints
-        self.pes = PES(atoms, constraints=constraints, trajectory=trajectory, eta=eta, v0=v0,
+        cls = CellCartesianPES if getattr(self, 'optimize_cell', False) else PES
+        self.pes = cls(atoms, constraints=constraints, trajectory=trajectory, eta=eta, v0=v0,
                        hessian_function=hessian_function, **kwargs)
         self.trajectory = self.pes.traj
 
@@ -247,14 +279,21 @@ class Sella(Optimizer):
         positions of the dummy atoms of internal coordinates."""
         H = self.pes.H
         dpos = self.pes.dpos
+        # cell runs: also the cell, its reference and the cell trust radius (files of other runs are unchanged)
+        cell = {} if not self.optimize_cell else dict(cell=np.array(self.pes.atoms.get_cell(), dtype=np.float64),
+                                                      orig_cell=self.pes.orig_cell, delta_cell=self.delta_cell)
         np.savez(filename, positions=self.pes.atoms.positions, dummies=np.zeros((0, 3)) if dpos is None else dpos,
                  B=(np.zeros((0, 0)) if H.B is None else H.B),
                  has_B=H.B is not None, H_initialized=H.initialized, delta=self.delta, rho=self.rho,
                  nsteps=self.nsteps, nsteps_since_diag=self.nsteps_since_diag, initialized=self.initialized,
-                 first_diag=self.pes.first_diag)
+                 first_diag=self.pes.first_diag, **cell)
 
     def load_state(self, filename):
         z = np.load(filename if str(filename).endswith('.npz') else str(filename) + '.npz')
+        if self.optimize_cell and 'cell' in z.files:
+            self.pes.atoms.set_cell(z['cell'].copy(), scale_atoms=False)
+            self.pes.orig_cell = z['orig_cell'].copy()
+            self.delta_cell = float(z['delta_cell'])
         self.pes.atoms.positions = z['positions'].copy()
         if self.pes.int is not None and 'dummies' in z.files and z['dummies'].shape == self.pes.int.dummies.shape:
             self.pes.int.dummies = z['dummies'].copy()
@@ -484,8 +523,13 @@ class Sella(Optimizer):
 
     # ---- ASE Optimizer protocol -------------------------------------------------------------------------------------
     def _verdict(self):
-        """(converged, fmax, cmax) at the threshold of the current run (0.05 before `run` set one)."""
-        self._last_converged = self.pes.converged(0.05 if self.fmax is None else self.fmax)
+        """(converged, fmax, cmax) at the threshold of the current run (0.05 before `run` set one); cell runs:
+        (converged, fmax, cmax, smax), the cell gradient judged against `smax` (default: fmax)."""
+        fmax = 0.05 if self.fmax is None else self.fmax
+        if self.optimize_cell:
+            self._last_converged = self.pes.converged(fmax, smax=fmax if self.smax is None else self.smax)
+        else:
+            self._last_converged = self.pes.converged(fmax)
         return self._last_converged
 
     def converged(self, forces=None):
@@ -494,20 +538,27 @@ class Sella(Optimizer):
     gradient_converged = converged            # newer ASE releases ask under this name
 
     def log(self, forces=None):
-        """One line per step: Step Time Energy fmax cmax rtrust rho (optimize.py:457-502)."""
+        """One line per step: Step Time Energy fmax cmax rtrust rho (optimize.py:457-502); cell runs: Step Time Energy
+        fmax smax cmax rtrust strust rho (:456-480)."""
         out = self.logfile
         if out is None:
             return
         verdict = self._last_converged
-        if verdict is None or len(verdict) != 3:
+        if verdict is None or len(verdict) != (4 if self.optimize_cell else 3):
             verdict = self._verdict()
         label = type(self).__name__
-        if self.nsteps == 0:
+        if self.optimize_cell:
+            heads = ("Step", "Time", "Energy", "fmax", "smax", "cmax", "rtrust", "strust", "rho")
+            values = (verdict[1], verdict[3], verdict[2], self.delta, self.delta_cell, self.rho)
+        else:
             heads = ("Step", "Time", "Energy", "fmax", "cmax", "rtrust", "rho")
-            out.write(" " * len(label) + "{:>4s} {:>8s} {:>15s} {:>12s} {:>12s} {:>12s} {:>12s}\n".format(*heads))
-        out.write("{} {:>3d} {:>8s} {:>15.6f} {:>12.4f} {:>12.4f} {:>12.4f} {:>12.4f}\n".format(
-            label, self.nsteps, strftime("%H:%M:%S", localtime()), self.pes.get_f(), verdict[1], verdict[2],
-            self.delta, self.rho))
+            values = (verdict[1], verdict[2], self.delta, self.rho)
+        if self.nsteps == 0:
+            out.write(" " * len(label) + "{:>4s} {:>8s} {:>15s}".format(*heads[:3])
+                      + "".join(" {:>12s}".format(h) for h in heads[3:]) + "\n")
+        out.write("{} {:>3d} {:>8s} {:>15.6f}".format(label, self.nsteps, strftime("%H:%M:%S", localtime()),
+                                                      self.pes.get_f())
+                  + "".join(" {:>12.4f}".format(v) for v in values) + "\n")
         flush = getattr(out, 'flush', None)
         if callable(flush):
             flush()

@@ -176,13 +176,19 @@ class RestrictedAtomicStep(BaseRestrictedStep):
                              f"the {self.__class__.__name__} trust region method.")
         BaseRestrictedStep.__init__(self, pes, *args, **kwargs)
 
+    @staticmethod
+    def _triples(v):
+        """v as rows of three; a trailing partial group (cell coordinates under a mask) is padded with zeros."""
+        pad = -len(v) % 3
+        return (v if pad == 0 else np.concatenate([v, np.zeros(pad)])).reshape((-1, 3))
+
     def cons(self, s, dsda=None):
-        per_atom = s.reshape((-1, 3))
+        per_atom = self._triples(s)
         sizes = np.sqrt(np.einsum('ij,ij->i', per_atom, per_atom))
         worst = int(sizes.argmax())
         if dsda is None:
             return sizes[worst]
-        return sizes[worst], float(dsda.reshape((-1, 3))[worst] @ per_atom[worst]) / max(sizes[worst], 1e-12)
+        return sizes[worst], float(self._triples(dsda)[worst] @ per_atom[worst]) / max(sizes[worst], 1e-12)
 
 
 class MaxInternalStep(BaseRestrictedStep):

@@ -9,7 +9,8 @@ preconditioner / TS-BFGS / P-RFO, the Davidson loop and the quasi-Newton updates
 Host-side (as in the reference, outside its accelerator seam): the rank-revealing pivoted QR
 of the (ncons x n) constraint Jacobian and O(n) vector algebra.
 
-Not restated here (out of the saddle-point scope): InternalPES / Cell*PES.
+Also here: `InternalPES` (redundant internal coordinates) and `CellCartesianPES` (positions and unit cell together,
+for minima).  Not restated: CellInternalPES.
 """
 import numpy as np
 from scipy.linalg import eigh, qr
@@ -988,3 +989,220 @@ class InternalPES(PES):
         # `bad_int` stays set and the caller — `Sella.step`, optimize.py:384-410 — rebuilds the coordinate system
         # from the geometry reached.
         return PES.kick(self, dx, diag=diag, **diag_kwargs)
+
+
+# ------------------------------------------------------------------------------------------------
+# CellCartesianPES — atomic positions and the unit cell together, for minima (sella/peswrapper.py:2376-2935).
+#
+# Coordinates x = [positions (3N), masked entries of L = logm(F) * exp_cell_factor], F = cell . orig_cell^-1 (the
+# log-deformation of ASE's FrechetCellFilter).  The gradient of the cell coordinates comes from the calculator's stress:
+# dE/dC = C^-T (V sigma + r^T f) at fixed Cartesian positions, dE/dF = dE/dC C0^T, and dE/dL through the Frechet
+# derivative of expm (Daleckii-Krein form).  The cell coordinates carry no constraints; the search runs through the
+# general driver (the fused step, the library finite-difference operator and the library search loop are for `PES`
+# itself).
+# ------------------------------------------------------------------------------------------------
+from scipy.linalg import expm, expm_frechet, logm  # noqa: E402
+
+from .atoms import voigt_to_matrix  # noqa: E402
+
+
+def logm_3x3(F):
+    """Principal logarithm of a real 3 x 3 matrix with positive eigenvalues, V diag(log lam) V^-1 from its
+    eigendecomposition; scipy's `logm` when the eigenvector matrix is ill-conditioned (nearly defective F)."""
+    lam, V = np.linalg.eig(F)
+    if np.linalg.cond(V) > 1e10:
+        return np.real(logm(F))
+    return np.real(V @ np.diag(np.log(lam.astype(complex))) @ np.linalg.inv(V))
+
+
+def expm_frechet_3x3_contracted(U, G):
+    """g_mn = sum_ab G_ab [D expm(U)[E_mn]]_ab for all nine unit directions E_mn: the gradient with respect to U of a
+    function whose gradient with respect to F = expm(U) is G.  For diagonalisable U = V diag(lam) V^-1 the Frechet
+    derivative is D expm(U)[E] = V (f o (V^-1 E V)) V^-1 with the divided differences f_ij = (e^lam_i - e^lam_j) /
+    (lam_i - lam_j) (e^lam_i on the diagonal and for equal eigenvalues; Daleckii-Krein), which contracts to
+    g = V^-T (f o (V^T G V^-T)) V^T.  U ~ 0 gives the identity map; an ill-conditioned eigenbasis falls back to
+    scipy's `expm_frechet`, direction by direction."""
+    if np.linalg.norm(U) < 1e-10:
+        return np.array(G, dtype=np.float64)
+    lam, V = np.linalg.eig(U)
+    if np.linalg.cond(V) > 1e10:
+        g = np.zeros((3, 3))
+        for m in range(3):
+            for n in range(3):
+                E = np.zeros((3, 3))
+                E[m, n] = 1.0
+                g[m, n] = np.sum(expm_frechet(U, E, compute_expm=False) * G)
+        return g
+    Vinv = np.linalg.inv(V)
+    el = np.exp(lam)
+    diff = lam[:, None] - lam[None, :]
+    distinct = np.abs(diff) > 1e-12 * max(np.abs(lam).max(), 1.0)
+    f = np.where(distinct, (el[:, None] - el[None, :]) / np.where(distinct, diff, 1.0), el[:, None])
+    return np.real(Vinv.T @ (f * (V.T @ G @ Vinv.T)) @ V.T)
+
+
+class CellCartesianPES(PES):
+    """`PES` with the unit cell as extra coordinates (Cartesian positions + masked log-deformation of the cell).
+
+    exp_cell_factor (default N) scales the log-deformation; cell_mask (3 x 3 bools, default all) selects the free
+    entries; scalar_pressure (eV / A^3) adds p V to the energy.  The initial Hessian is the user's H0, else 70 I on the
+    positions and 1 I on the cell; refine_initial_hessian fills the cell columns by central differences (2 n_cell_dof
+    evaluations, step hessian_delta); save_hessian names an .npy file for it."""
+
+    def __init__(self, atoms, H0=None, constraints=None, eigensolver='jd0', trajectory=None, eta=1e-4, v0=None,
+                 proj_trans=None, proj_rot=None, hessian_function=None, exp_cell_factor=None, cell_mask=None,
+                 scalar_pressure=0.0, refine_initial_hessian=False, hessian_delta=1e-5, save_hessian=None):
+        self.orig_cell = np.array(atoms.get_cell(), dtype=np.float64)
+        self.exp_cell_factor = float(len(atoms)) if exp_cell_factor is None else float(exp_cell_factor)
+        mask = np.ones((3, 3), dtype=bool) if cell_mask is None else np.asarray(cell_mask, dtype=bool).reshape((3, 3))
+        self.cell_mask = mask
+        self.n_cell_dof = int(mask.sum())
+        self.scalar_pressure = float(scalar_pressure)
+        PES.__init__(self, atoms, H0=None, constraints=constraints, eigensolver=eigensolver, trajectory=trajectory,
+                     eta=eta, v0=v0, proj_trans=proj_trans, proj_rot=proj_rot, hessian_function=hessian_function)
+        nc = self.ncart
+        self.dim = nc + self.n_cell_dof
+        if H0 is not None:
+            H0 = np.asarray(H0, dtype=np.float64)
+            if H0.shape == (nc, nc):                             # positions only: the cell block as by default
+                full = np.eye(self.dim)
+                full[:nc, :nc] = H0
+                H0 = full
+        else:
+            H0 = np.eye(self.dim)
+            H0[:nc, :nc] *= 70.0
+            if refine_initial_hessian:
+                cols = self._cell_hessian_columns(hessian_delta)
+                H0[:nc, nc:] = cols[:nc]
+                H0[nc:, :nc] = cols[:nc].T
+                H0[nc:, nc:] = 0.5 * (cols[nc:] + cols[nc:].T)
+        if save_hessian is not None:
+            np.save(save_hessian, H0)
+        self.set_H(H0, initialized=True)
+
+    def _cell_hessian_columns(self, delta):
+        """Hessian columns of the cell coordinates by central differences of the gradient (dim x n_cell_dof)."""
+        nc = self.ncart
+        cols = np.zeros((self.dim, self.n_cell_dof))
+        x0 = self.get_x()
+        self.save()
+        for k in range(self.n_cell_dof):
+            gs = []
+            for sign in (1.0, -1.0):
+                x = x0.copy()
+                x[nc + k] += sign * delta
+                self.set_x(x)
+                gs.append(self.eval()[1])
+                self.restore()
+            cols[:, k] = (gs[0] - gs[1]) / (2.0 * delta)
+        self.curr = dict.fromkeys(('x', 'f', 'g'))
+        self.last = dict(self.curr)
+        return cols
+
+    # ---- cell coordinates --------------------------------------------------------------------------------------------
+    def _cell(self):
+        return np.array(self.atoms.get_cell(), dtype=np.float64)
+
+    def _log_deform(self):
+        """L = logm(cell . orig_cell^-1) * exp_cell_factor (3 x 3)."""
+        return logm_3x3(self._cell() @ np.linalg.inv(self.orig_cell)) * self.exp_cell_factor
+
+    def _set_cell_params(self, params):
+        L = self._log_deform()
+        L[self.cell_mask] = params
+        self.atoms.set_cell(expm(L / self.exp_cell_factor) @ self.orig_cell, scale_atoms=False)
+
+    def get_x(self):
+        return np.concatenate([self.apos.ravel(), self._log_deform()[self.cell_mask]])
+
+    def set_x(self, target):
+        """The cell first, then the Cartesian positions (not scaled with the cell)."""
+        nc = self.ncart
+        x0 = self.get_x()
+        self._set_cell_params(target[nc:])
+        self.atoms.positions = target[:nc].reshape((-1, 3))
+        dx = target - x0
+        g = self.curr.get('g')
+        return dx, dx.copy(), (np.zeros(self.dim) if g is None else g.copy())
+
+    def save(self):
+        PES.save(self)
+        self.savepoint['cell'] = self._cell()
+
+    def restore(self):
+        kept = self.savepoint.get('cell')
+        if kept is not None:
+            self.atoms.set_cell(kept, scale_atoms=False)
+        PES.restore(self)
+
+    # ---- the calculator boundary -------------------------------------------------------------------------------------
+    def eval(self):
+        """Energy (+ p V) and gradient [dE/dr, dE/dparams]; the stress is asked for first, so that a calculator that
+        computes everything in one go (EMT) is called once."""
+        self.neval += 1
+        stress = np.asarray(self.atoms.get_stress(), dtype=np.float64)
+        f = float(self.atoms.get_potential_energy())
+        forces = np.asarray(self.atoms.get_forces(), dtype=np.float64).reshape((-1, 3))
+        if self.scalar_pressure != 0.0:
+            f += self.scalar_pressure * self.atoms.get_volume()
+        g = np.concatenate([-forces.ravel(), self._cell_gradient(stress, forces)])
+        self.write_traj()
+        return f, g
+
+    def _cell_gradient(self, stress, forces):
+        sigma = voigt_to_matrix(stress) if np.size(stress) == 6 else np.asarray(stress, dtype=np.float64).reshape(3, 3)
+        sigma = sigma + self.scalar_pressure * np.eye(3)
+        C = self._cell()
+        volume = abs(np.linalg.det(C))
+        pos = np.asarray(self.atoms.positions, dtype=np.float64)
+        dEdC = np.linalg.solve(C.T, volume * sigma + pos.T @ forces)     # at fixed Cartesian positions
+        dEdF = dEdC @ self.orig_cell.T                                   # C = F C0
+        U = logm_3x3(C @ np.linalg.inv(self.orig_cell))
+        g = expm_frechet_3x3_contracted(U, dEdF)
+        return g[self.cell_mask] / self.exp_cell_factor
+
+    # ---- constraints: they act on the positions only ------------------------------------------------------------
+    def get_drdx(self):
+        drdx = PES.get_drdx(self)
+        out = np.zeros((drdx.shape[0], self.dim))
+        out[:, :self.ncart] = drdx
+        return out
+
+    def get_Hc(self):
+        Hc = PES.get_Hc(self)
+        out = np.zeros((self.dim, self.dim))
+        out[:self.ncart, :self.ncart] = Hc
+        return out
+
+    def _calc_basis(self):
+        key = self._state_hash()
+        cached = self._basis_cache.get(key)
+        if cached is not None:
+            return cached
+        nc, ncell = self.ncart, self.n_cell_dof
+        Ucons_c, Ufree_c = _split_cons_subspace(PES.get_drdx(self))
+        Ucons = np.zeros((self.dim, Ucons_c.shape[1]))
+        Ucons[:nc] = Ucons_c
+        Ufree = np.zeros((self.dim, Ufree_c.shape[1] + ncell))
+        Ufree[:nc, :Ufree_c.shape[1]] = Ufree_c
+        Ufree[nc:, Ufree_c.shape[1]:] = np.eye(ncell)
+        result = (self.get_drdx(), Ucons, shared_identity(self.dim), Ufree)
+        self._basis_cache.put(key, result)
+        return result
+
+    def get_projected_forces(self):
+        g = self.get_g()[:self.ncart]
+        Uc = self.get_Ufree()[:self.ncart]
+        return -(Uc @ (Uc.T @ g)).reshape((-1, 3))
+
+    def converged(self, fmax, smax=None, cmax=1e-5):
+        """(done, largest projected force on an atom, norm of the constraint residual, largest |cell gradient|) —
+        the reference's order; smax defaults to fmax."""
+        smax = fmax if smax is None else smax
+        per_atom = self.get_projected_forces()
+        worst_force = float(np.sqrt(np.einsum('ij,ij->i', per_atom, per_atom).max()))
+        g_cell = self.get_g()[self.ncart:]
+        worst_cell = float(np.abs(g_cell).max()) if g_cell.size else 0.0
+        violation = float(np.linalg.norm(self.get_res()))
+        return (bool(worst_force < fmax and worst_cell < smax and violation < cmax), worst_force, violation,
+                worst_cell)

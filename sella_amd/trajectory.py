@@ -207,8 +207,9 @@ def _calculator_results(atoms):
     name = getattr(calc, 'name', None) or type(calc).__name__.lower()
     if isinstance(calc, SinglePointResults):
         return name, calc.energy, calc.forces
+    from .atoms import cache_key
     res = getattr(calc, '_res', None)
-    if res is not None and getattr(calc, '_key', None) == atoms.positions.tobytes():
+    if res is not None and getattr(calc, '_key', None) == cache_key(atoms):
         return name, float(res[0]), -np.asarray(res[1], dtype=float).reshape(-1, 3)
     results = getattr(calc, 'results', None)                     # an ASE calculator, if one is attached
     if isinstance(results, dict) and 'energy' in results and not getattr(calc, 'calculation_required',
