@@ -435,6 +435,8 @@ int sella_internals_tric_eval_shifted(sella_ctx* ctx, int natoms, int nf, const 
  *   rdot(x): rows H_k x, (ncoords x 3 natoms), linalg.py:620-640;  ddot(u, x): u . H_k x (ncoords), :642-646;
  *   hess_dense: the dense H_k of coordinates first .. first+count as (count 3 natoms x 3 natoms) rows, :420-442, 595-596;
  *   jac_dense (count x 3 natoms) / jac_matvec (ncoords) / jac_rmatvec (3 natoms, add.at order): :377-401.
+ *   ldot_acc(v, alpha, beta): out = beta out + alpha ldot(v), the sum formed exactly as by ldot and added once per
+ *     element (out is not read when beta == 0: (1, 0) stores what ldot stores, bit for bit).
  * `out` matrices are allocated by the caller with exactly the shapes above; every element, padding included, is
  * stored.  Invalid shapes: SELLA_E_INVALID; a failed allocation: SELLA_E_NOMEM.                                    */
 typedef struct sella_sparse_int sella_sparse_int;
@@ -446,12 +448,31 @@ int sella_sparse_int_get_values(sella_sparse_int* s, double* grad_vals, double* 
 int sella_sparse_int_eval(sella_sparse_int* s, int first, int count, int natoms_per_coord, const double* pos,
                           const double* tvec, int hessian);
 int sella_sparse_int_ldot(sella_sparse_int* s, const double* v, sella_mat out);
+int sella_sparse_int_ldot_acc(sella_sparse_int* s, const double* v, double alpha, double beta, sella_mat out);
 int sella_sparse_int_rdot(sella_sparse_int* s, const double* x, sella_mat out);
 int sella_sparse_int_ddot(sella_sparse_int* s, const double* u, const double* x, double* out);
 int sella_sparse_int_hess_dense(sella_sparse_int* s, int first, int count, sella_mat out);
 int sella_sparse_int_jac_dense(sella_sparse_int* s, int first, int count, sella_mat out);
 int sella_sparse_int_jac_matvec(sella_sparse_int* s, const double* x, double* out);
 int sella_sparse_int_jac_rmatvec(sella_sparse_int* s, const double* y, double* out);
+
+/* ---- exact Hessians in internal coordinates ------------------------------------------------------ */
+/* The Cartesian Hessian of a calculator in the redundant internal coordinates of a topology `s` whose gradient and
+ * Hessian blocks hold B = dq/dx and the d2q_i/dx2 of the current geometry, and back
+ * (InternalPES._convert_cartesian_hessian_to_internal / _convert_internal_hessian_to_cartesian,
+ * sella/peswrapper.py:1247-1282).  n = 3 natoms of `s` (real atoms and dummies), nint = ncoords of `s`, g (nint, host)
+ * the internal gradient.
+ *   cart_to_int: Hcart (n x n) is overwritten with Hcorr = Hcart - sum_i g_i d2q_i/dx2 (one accumulating ldot);
+ *     X (n x r) = V_r S_r^-1 and Q (nint x r) = U_r from the singular value decomposition of B restricted to the real
+ *     atoms' columns (rows of X of dummy degrees of freedom zero, like the rows and columns of Hcart);
+ *     Hnred = X^T Hcorr X (r x r), lambda_bar = exp(mean log |eig((Hnred + Hnred^T) / 2)|) (the r eigenvalues are the
+ *     only read-back), out (nint x nint) = Q (Hnred - lambda_bar I) Q^T + lambda_bar I, left on the device.
+ *     r = 0: SELLA_E_INVALID.
+ *   int_to_cart: out (n x n) = B^T Hint B + sum_i g_i d2q_i/dx2, Hint (nint x nint).
+ * All matrices are allocated by the caller with exactly these shapes; invalid shapes: SELLA_E_INVALID.              */
+int sella_hessian_cart_to_int(sella_ctx* ctx, sella_sparse_int* s, const double* g, sella_mat Hcart, sella_mat X,
+                              sella_mat Q, sella_mat out, double* lambda_bar);
+int sella_hessian_int_to_cart(sella_ctx* ctx, sella_sparse_int* s, const double* g, sella_mat Hint, sella_mat out);
 
 /* ---- EMT calculator (far side of the calculator boundary, sella/peswrapper.py:413-418) -------------- */
 /* Energy and gradient of the effective-medium potential (functional form of ase/calculators/emt.py).

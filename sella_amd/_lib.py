@@ -159,12 +159,15 @@ SIGNATURES = {
     'sella_sparse_int_get_values': (c_int, [c_void_p, c_void_p, c_void_p]),
     'sella_sparse_int_eval': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int]),
     'sella_sparse_int_ldot': (c_int, [c_void_p, c_void_p, c_int]),
+    'sella_sparse_int_ldot_acc': (c_int, [c_void_p, c_void_p, c_double, c_double, c_int]),
     'sella_sparse_int_rdot': (c_int, [c_void_p, c_void_p, c_int]),
     'sella_sparse_int_ddot': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'sella_sparse_int_hess_dense': (c_int, [c_void_p, c_int, c_int, c_int]),
     'sella_sparse_int_jac_dense': (c_int, [c_void_p, c_int, c_int, c_int]),
     'sella_sparse_int_jac_matvec': (c_int, [c_void_p, c_void_p, c_void_p]),
     'sella_sparse_int_jac_rmatvec': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'sella_hessian_cart_to_int': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double_p]),
+    'sella_hessian_int_to_cart': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int]),
     'sella_emt_eval': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
                                c_double, c_double_p, c_void_p]),
     'sella_emt_eval_stress': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double,

@@ -428,6 +428,9 @@ int lr_lowrank_update(sella_ctx* c, int n, int* r_io, double* mu, double lam0, M
 // too when not null.  No wait (sella_sparse_int_eval writes straight into the buffers of its topology).
 int internals_queue(sella_ctx* c, int natoms, int nc, const double* dpos, const double* dtv, double* dq, double* dgrad,
                     double* dhess);
+// sparse_internal.hip: the dimensions of a topology (-1 for a null object)
+int sparse_int_ncoords(const sella_sparse_int* s);
+int sparse_int_natoms(const sella_sparse_int* s);
 // emt.hip: sella_emt_eval with the parameter table and shift vectors optionally resident (dconst: 9 n + 3 nshift doubles);
 // virial6 != nullptr: the six summed virial components too (sella_emt_eval_stress)
 int emt_eval_resident(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,

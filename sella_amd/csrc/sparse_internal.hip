@@ -77,11 +77,15 @@ int obj_upload(sella_sparse_int* s, const std::vector<T>& host, T** p) {
 constexpr int LDOT_LCAP = 2048;    // pair lists of up to this many column atoms are searched in LDS
 
 // ldot: out[3A+i, 3B+j] = sum over size groups g (first appearance) of (sum over the contributions of g to (A, B), in
-// coordinate, a, b order, of H_c[a,i,b,j] * v_c) — every product rounded, each group's sum from 0.0 (linalg.py:613-618)
-__global__ __launch_bounds__(256) void sparse_ldot_kernel(int ndof, int ld, const long* __restrict__ pptr,
-                                                          const int* __restrict__ pcol, const long* __restrict__ cptr,
-                                                          const Contrib* __restrict__ ctb, const double* __restrict__ v,
-                                                          const double* __restrict__ hess, double* __restrict__ out) {
+// coordinate, a, b order, of H_c[a,i,b,j] * v_c) — every product rounded, each group's sum from 0.0 (linalg.py:613-618).
+// ACC: the same sum, then out = beta * out + alpha * sum, once per element (out is not read when beta == 0); ACC = false
+// is the plain store of the reference contraction.
+template <bool ACC>
+__device__ __forceinline__ void sparse_ldot_body(int ndof, int ld, const long* __restrict__ pptr,
+                                                 const int* __restrict__ pcol, const long* __restrict__ cptr,
+                                                 const Contrib* __restrict__ ctb, const double* __restrict__ v,
+                                                 const double* __restrict__ hess, double* __restrict__ out, double alpha,
+                                                 double beta) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -123,8 +127,22 @@ __global__ __launch_bounds__(256) void sparse_ldot_kernel(int ndof, int ld, cons
                 tot += part;
             }
         }
-        row[s] = tot;
+        if constexpr (ACC) row[s] = beta == 0.0 ? alpha * tot : beta * row[s] + alpha * tot;
+        else row[s] = tot;
     }
+}
+__global__ __launch_bounds__(256) void sparse_ldot_kernel(int ndof, int ld, const long* __restrict__ pptr,
+                                                          const int* __restrict__ pcol, const long* __restrict__ cptr,
+                                                          const Contrib* __restrict__ ctb, const double* __restrict__ v,
+                                                          const double* __restrict__ hess, double* __restrict__ out) {
+    sparse_ldot_body<false>(ndof, ld, pptr, pcol, cptr, ctb, v, hess, out, 1.0, 0.0);
+}
+__global__ __launch_bounds__(256) void sparse_ldot_acc_kernel(int ndof, int ld, const long* __restrict__ pptr,
+                                                              const int* __restrict__ pcol, const long* __restrict__ cptr,
+                                                              const Contrib* __restrict__ ctb, const double* __restrict__ v,
+                                                              const double* __restrict__ hess, double* __restrict__ out,
+                                                              double alpha, double beta) {
+    sparse_ldot_body<true>(ndof, ld, pptr, pcol, cptr, ctb, v, hess, out, alpha, beta);
 }
 
 // rdot: out[c, 3B+j] = sum over a with atoms_c[a] == B of sum_{b, j'} H_c[a,j,b,j'] x[3 atoms_c[b] + j'] (linalg.py:620-640)
@@ -451,9 +469,12 @@ extern "C" int sella_sparse_int_eval(sella_sparse_int* s, int first, int count, 
     return stream_wait(c);
 }
 
-extern "C" int sella_sparse_int_ldot(sella_sparse_int* s, const double* v, sella_mat out) {
+namespace sella {
+namespace {
+// ldot into `out` (3 natoms x 3 natoms): the reference store (acc == false) or out = beta out + alpha sum (acc == true)
+int ldot_launch(sella_sparse_int* s, const double* v, sella_mat out, bool acc, double alpha, double beta) {
     if (!s || (s->nc > 0 && !v)) return SELLA_E_INVALID;
-    Mat* m = out_mat(s, out, 3L * s->natoms, "sparse_int_ldot");
+    Mat* m = out_mat(s, out, 3L * s->natoms, acc ? "sparse_int_ldot_acc" : "sparse_int_ldot");
     if (!m) return SELLA_E_INVALID;
     sella_ctx* c = s->c;
     SCHK(ensure_hess(s));
@@ -462,13 +483,31 @@ extern "C" int sella_sparse_int_ldot(sella_sparse_int* s, const double* v, sella
     double* dv;
     SCHK(stage_vec(c, SCR_MISC1, v, (size_t)s->nc, &dv));
     const int ndof = 3 * s->natoms;
-    // algorithmic bytes: the dense matrix written, every Hessian value read once
-    prof_begin(c, PROF_OTHER, 8.0 * ((double)ndof * m->ld + s->hoff[s->nc] + s->nc), 2.0 * s->hoff[s->nc]);
-    SELLA_LAUNCH(c, sparse_ldot_kernel, dim3((unsigned)ndof), dim3(256), 0, ndof, m->ld, s->d_pptr, s->d_pcol, s->d_cptr,
-                 s->d_ctb, dv, s->d_hess, m->d);
+    // algorithmic bytes: the dense matrix written (and read when accumulating), every Hessian value read once
+    prof_begin(c, PROF_OTHER, 8.0 * ((acc && beta != 0.0 ? 2.0 : 1.0) * ndof * m->ld + s->hoff[s->nc] + s->nc),
+               2.0 * s->hoff[s->nc]);
+    if (acc)
+        SELLA_LAUNCH(c, sparse_ldot_acc_kernel, dim3((unsigned)ndof), dim3(256), 0, ndof, m->ld, s->d_pptr, s->d_pcol,
+                     s->d_cptr, s->d_ctb, dv, s->d_hess, m->d, alpha, beta);
+    else
+        SELLA_LAUNCH(c, sparse_ldot_kernel, dim3((unsigned)ndof), dim3(256), 0, ndof, m->ld, s->d_pptr, s->d_pcol,
+                     s->d_cptr, s->d_ctb, dv, s->d_hess, m->d);
     prof_end(c);
     HIPCHK(hipGetLastError());
     return stream_wait(c);
+}
+}  // namespace
+
+int sparse_int_ncoords(const sella_sparse_int* s) { return s ? s->nc : -1; }
+int sparse_int_natoms(const sella_sparse_int* s) { return s ? s->natoms : -1; }
+}  // namespace sella
+
+extern "C" int sella_sparse_int_ldot(sella_sparse_int* s, const double* v, sella_mat out) {
+    return ldot_launch(s, v, out, false, 1.0, 0.0);
+}
+
+extern "C" int sella_sparse_int_ldot_acc(sella_sparse_int* s, const double* v, double alpha, double beta, sella_mat out) {
+    return ldot_launch(s, v, out, true, alpha, beta);
 }
 
 extern "C" int sella_sparse_int_rdot(sella_sparse_int* s, const double* x, sella_mat out) {

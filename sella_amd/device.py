@@ -552,6 +552,25 @@ class Context:
         self._drain()
         return DeviceSparseInternals(self, natoms, sizes, atoms)
 
+    # ---- exact Hessians in internal coordinates ----------------------------------------------------------
+    def hessian_cart_to_int(self, sparse, g, Hcart, X, Q):
+        """(H_int DeviceMatrix (nint x nint), lambda_bar): the Cartesian Hessian Hcart (n x n DeviceMatrix, n = 3 natoms
+        of the `DeviceSparseInternals` topology `sparse`, overwritten with Hcart - sum_i g_i d2q_i/dx2) in the internal
+        coordinates, X (n x r) = V_r S_r^-1 and Q (nint x r) = U_r the thin singular factors of B (`sella_hessian_cart_to_int`)."""
+        g = as_f64(g, (sparse.ncoords,))
+        out = self.zeros(sparse.ncoords, sparse.ncoords)
+        lam = c_double(0.0)
+        check(_lib.lib().sella_hessian_cart_to_int(self._h, sparse._h, ptr(g), Hcart.handle, X.handle, Q.handle,
+                                                   out.handle, byref(lam)))
+        return out, lam.value
+
+    def hessian_int_to_cart(self, sparse, g, Hint):
+        """B^T Hint B + sum_i g_i d2q_i/dx2 as an (n x n) DeviceMatrix (`sella_hessian_int_to_cart`)."""
+        g = as_f64(g, (sparse.ncoords,))
+        out = self.zeros(sparse.ndof, sparse.ndof)
+        check(_lib.lib().sella_hessian_int_to_cart(self._h, sparse._h, ptr(g), Hint.handle, out.handle))
+        return out
+
     # ---- EMT calculator -------------------------------------------------------------------------
     def emt_eval(self, pos, par, shifts, rc, acut, cutoff, beta):
         """(energy, gradient (n, 3)) of the EMT potential; par (9, n), shifts (nshift, 3)."""
@@ -712,6 +731,13 @@ class DeviceSparseInternals:
         v = as_f64(v, (self.ncoords,))
         out = self._out(out, self.ndof)
         check(_lib.lib().sella_sparse_int_ldot(self._h, ptr(v), out.handle))
+        return out
+
+    def ldot_acc(self, v, out, alpha=1.0, beta=1.0):
+        """out = beta out + alpha ldot(v) in place (the sum formed exactly as by `ldot`; out is not read when beta == 0)."""
+        v = as_f64(v, (self.ncoords,))
+        out = self._out(out, self.ndof)
+        check(_lib.lib().sella_sparse_int_ldot_acc(self._h, ptr(v), float(alpha), float(beta), out.handle))
         return out
 
     def rdot(self, x, out=None):

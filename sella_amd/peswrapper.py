@@ -716,6 +716,7 @@ class InternalPES(PES):
         kwargs.pop('proj_trans', None)
         kwargs.pop('proj_rot', None)
         self._factor_cache = _LRU2()
+        self._real_factor_cache = _LRU2()
         self._Hc_cache = _LRU2()
         PES.__init__(self, atoms, *args, constraints=new_int.cons, H0=None, proj_trans=False, proj_rot=False,
                      **kwargs)
@@ -983,6 +984,66 @@ class InternalPES(PES):
             return
         self.curr.update(B=self._get_factor().Bs)
         return True
+
+    # ---- exact Hessians: hessian_function in internal coordinates (:1247-1288) -----------------------------------
+    def _get_real_factor(self):
+        """The spectral factor of B[:, :3N], the columns of the real atoms (the PES's own factor without dummies)."""
+        if not self.int.ndummies:
+            return self._get_factor()
+        key = self._state_hash()
+        cached = self._real_factor_cache.get(key)
+        if cached is None:
+            cached = _BFactor(self.int.jacobian_csr()[:, :3 * len(self.atoms)])
+            self._real_factor_cache.put(key, cached)
+        return cached
+
+    def _convert_cartesian_hessian_to_internal(self, Hcart):
+        """The internal-coordinate Hessian of the Cartesian Hessian Hcart (3N x 3N, real atoms) as a `DeviceMatrix`
+        (nint x nint): with B = B[:, :3N] = U_r S_r V_r^T (singular values above 1e-6), X = V_r S_r^-1 and Q = U_r,
+        Hnred = X^T (Hcart - sum_i g_i d2q_i/dx2) X and lambda_bar the geometric mean of |eig(Hnred)|, the result is
+        Q Hnred Q^T + lambda_bar (I - Q Q^T) — the reference's Unred Hnred Unred^T + lambda_bar Ured Ured^T.  lambda_bar is
+        taken from the eigenvalues of the symmetric part of Hnred, which for an asymmetric Hcart (finite differences)
+        differ from those of the one triangle the reference's eigh reads.  Runs on the device
+        (`sella_hessian_cart_to_int`); dummy degrees of freedom enter as zero rows and columns of Hcart and zero rows of
+        X."""
+        n, nx = 3 * len(self.atoms), self.int.ndof
+        Hcart = np.asarray(Hcart, dtype=np.float64)
+        if Hcart.shape != (n, n):
+            raise ValueError(f'hessian_function must return the {n} x {n} Cartesian Hessian of the {len(self.atoms)} '
+                             f'atoms, got an array of shape {Hcart.shape}')
+        fac = self._get_real_factor()
+        X, Q = fac.BinvQ, fac.Q
+        if nx != n:
+            Hcart = np.pad(Hcart, ((0, nx - n), (0, nx - n)))
+            X = np.pad(X, ((0, nx - n), (0, 0)))
+        g = self.get_g()
+        hess = self.int.sparse_hessians()                  # B and the d2q_i/dx2 of this geometry, on the device
+        ctx = get_context()
+        hH, hX, hQ = ctx.upload(Hcart), ctx.upload(X), ctx.upload(Q)
+        try:
+            out, _ = ctx.hessian_cart_to_int(hess._device(), g, hH, hX, hQ)
+        finally:
+            for h in (hH, hX, hQ):
+                h.free()
+        return out
+
+    def _convert_internal_hessian_to_cartesian(self, Hint):
+        """B^T Hint B + sum_i g_i d2q_i/dx2 over all Cartesian degrees of freedom, dummies included (3(N + D) square), as
+        a `DeviceMatrix`; Hint (nint x nint) a `DeviceMatrix` or an array (`sella_hessian_int_to_cart`)."""
+        from .device import DeviceMatrix
+        ctx = get_context()
+        g = self.get_g()
+        own = not isinstance(Hint, DeviceMatrix)
+        hI = ctx.upload(np.asarray(Hint, dtype=np.float64)) if own else Hint
+        try:
+            return ctx.hessian_int_to_cart(self.int.sparse_hessians()._device(), g, hI)
+        finally:
+            if own:
+                hI.free()
+
+    def calculate_hessian(self):
+        assert self.hessian_function is not None
+        self.H.set_B(self._convert_cartesian_hessian_to_internal(self.hessian_function(self.atoms)))
 
     def kick(self, dx, diag=False, **diag_kwargs):
         # A geodesic that runs into a degenerate internal coordinate (an angle close to 0 or pi) stops there:
