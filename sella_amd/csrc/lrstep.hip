@@ -1464,8 +1464,11 @@ int lr_fused_step(sella_ctx* c, sella_opt_step_t* a, bool* handled, CalcPipe* pi
     }
     F.want_modes = propose && !view; F.slot_ws = SCR_EIG0; F.slot_panel = SCR_EIG1;
     // the view job depends on the full-space job up to its lr_pre_plan_kernel only: from there the two run side by side
+    // (not on a cohort member: its batchable launches are parked for the cohort stream, while plain launches such as the
+    // gemm of W+ = Q^T E would go to the second stream, which has not waited for them)
     bool overlap = false;
-    if (view && c->opt.lr_overlap && c->opt.lr_chain && (n + LR_CHUNK - 1) / LR_CHUNK <= LR_MAXPARTS) {
+    if (view && c->opt.lr_overlap && c->opt.lr_chain && (n + LR_CHUNK - 1) / LR_CHUNK <= LR_MAXPARTS &&
+        !(c->cohort && cohort_in_fiber())) {
         if (!c->stream2) {
             if (hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
