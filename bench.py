@@ -5,6 +5,11 @@
                                                              talk through librccl bound with ctypes, sella_amd/comm.py)
     python bench.py ... --dump-outputs DIR                  (also writes what the last timed step returned, rank 0's
                                                              replica, as DIR/<name>.npy in float64: see dump_outputs)
+    python bench.py ... --full                              (also runs every other leg: see "With --full" below)
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps, writes
+the dump if asked, and prints one JSON line with the headline fields, the run's configuration and `collective`
+(which binding carried the multi-rank exchanges: direct RCCL or the torch.distributed fallback).
 
 Metric (BASELINE.json): Davidson iterations per second on the synthetic 3N = 3072 Hessian of
 SURVEY.md §8(d).  One *step* = one complete `rayleigh_ritz(A, gamma=0.1, P, v0=g, 'jd0',
@@ -17,14 +22,15 @@ problems of the same recipe, because the exit iteration of one gamma = 0.1 run i
 vectors for the same matrices) and the per-call eigh is amortised over it.  Ranks are independent replicas (the path has
 no exchange step), so scaling is weak.
 
-Extra objects on the JSON line:
+With --full, the same line also carries what the other legs measure and check, each in runs of its own after the
+timed steps: the Davidson loop alone, the device eigh and the upload by themselves, several problems in flight, the
+optimizer and ensemble legs, parity against the host, and these objects:
   roofline      the dominant kernel of the step (`trd_gemv_kernel`, the trailing-matrix matvec of the eigh of P):
                 algorithmic bytes per launch (8 m^2) / mean launch time from hipEvents attached to the dispatch
                 packets on the library's own stream, collected in a separate instrumented pass; the Davidson
                 loop's own n x n streams are reported beside it.
   block_davidson  BASELINE configs[4]: block Davidson (16 vectors per iteration, H.V panel on the matrix cores) at
                 3N = 12288, rows of H sharded over the ranks (strong scaling), time per block iteration.
-  collective    which binding carried the multi-rank exchanges (direct RCCL or the torch.distributed fallback).
   cpu_baseline  the NumPy/SciPy oracle port of the reference algorithm (dense LU per iteration)
                 timed on this box's host cores on the same inputs (one call), rank 0 at N = 1 only.
 """
@@ -76,6 +82,42 @@ def dump_outputs(directory, step_out):
         arrays['rows'] = rows
     for name, a in arrays.items():
         np.save(os.path.join(directory, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def gather_timing(comm, world, elapsed, iters):
+    """(slowest rank's time for the timed steps, Davidson iterations summed over the ranks); every rank calls it."""
+    times = [elapsed]
+    total_iters = iters
+    if world > 1:
+        gathered = comm.allgather_host(np.array([elapsed, float(iters)]))     # RCCL all-gather of the per-replica results
+        times = [float(x[0]) for x in gathered]
+        total_iters = int(sum(float(x[1]) for x in gathered))
+    return max(times), total_iters
+
+
+def headline(args, n, world, comm, tmax, total_iters):
+    """The fields of the JSON line that a plain run prints (the --full legs add theirs behind them)."""
+    return {
+        'metric': 'Davidson iterations/s (3N=3072 synthetic Hessian, jd0, gamma=0.1, maxiter=40; '
+                  'whole rayleigh_ritz call incl. device eigh of the preconditioner)',
+        'value': round(total_iters / tmax, 2), 'unit': 'davidson_iter/s', 'n_gpus': world, 'steps': args.steps,
+        'warmup': args.warmup, 'ms_per_step': round(1e3 * tmax / args.steps, 3),
+        'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
+        'data': 'synthetic',
+        'config': {'workload': f'1024-atom-equivalent 3N={n} fp64 Davidson (BASELINE configs[1]), '
+                               f'one independent replica per GPU', 'n': n, 'maxiter': args.maxiter,
+                   'gamma': args.gamma, 'method': 'jd0', 'problems': args.seeds * args.starts, 'matrices': args.seeds,
+                   'vectors_per_call': round(total_iters / (args.steps * world), 2),
+                   **({'options': list(args.option)} if args.option else {})},
+        'collective': {'kind': comm.kind, 'nranks': getattr(comm, 'nranks', comm.world)},
+    }
+
+
+def close_comm(comm):
+    comm.barrier()
+    comm.close()
+    if comm.kind == 'torch.distributed':
+        comm.dist.destroy_process_group()
 
 
 class EnsembleMember:
@@ -164,6 +206,9 @@ def main():
     ap.add_argument('--gamma', type=float, default=0.1)
     ap.add_argument('--seeds', type=int, default=4)
     ap.add_argument('--starts', type=int, default=5)
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other leg (loop alone, eigh, upload, concurrent problems, '
+                         'optimizer, ensemble, block Davidson, roofline, parity, CPU baseline) and report them on the line')
     ap.add_argument('--converged-n', type=int, default=768)
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--option', action='append', default=[], metavar='KEY=VALUE',
@@ -295,6 +340,12 @@ def main():
     barrier()
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, out)        # `out`: the last timed step's result
+    if not args.full:
+        tmax, total_iters = gather_timing(comm, world, elapsed, iters)
+        if rank == 0:
+            print(json.dumps(headline(args, n, world, comm, tmax, total_iters)), flush=True)
+        close_comm(comm)
+        return
 
     # Davidson loop alone (P's eigendecomposition kept from a previous optimizer phase).  Measured here, in the state the
     # timed loop above ran in: behind the threaded leg below every call of this process is ~0.16 ms slower for a while
@@ -839,13 +890,7 @@ def main():
                 block_stats['eigh_exact_note'] = str(e)[:120]
         _dev2._default = None
 
-    times = [elapsed]
-    total_iters = iters
-    if world > 1:
-        gathered = comm.allgather_host(np.array([elapsed, float(iters)]))     # RCCL all-gather of the per-replica results
-        times = [float(x[0]) for x in gathered]
-        total_iters = int(sum(float(x[1]) for x in gathered))
-    tmax = max(times)
+    tmax, total_iters = gather_timing(comm, world, elapsed, iters)
 
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
@@ -901,19 +946,8 @@ def main():
                                   loop_only_gbs=round(24.0 * n * n * (it2 / t_loop) / 1e9, 1),
                                   loop_only_frac=round(24.0 * n * n * (it2 / t_loop) / 1e9 / HBM_PEAK_GBS, 4))
     if rank == 0:
-        value = total_iters / tmax
-        line = {
-            'metric': 'Davidson iterations/s (3N=3072 synthetic Hessian, jd0, gamma=0.1, maxiter=40; '
-                      'whole rayleigh_ritz call incl. device eigh of the preconditioner)',
-            'value': round(value, 2), 'unit': 'davidson_iter/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(1e3 * tmax / args.steps, 3),
-            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64',
-            'data': 'synthetic',
-            'config': {'workload': f'1024-atom-equivalent 3N={n} fp64 Davidson (BASELINE configs[1]), '
-                                   f'one independent replica per GPU', 'n': n, 'maxiter': args.maxiter,
-                       'gamma': args.gamma, 'method': 'jd0', 'problems': args.seeds * args.starts, 'matrices': args.seeds,
-                       'vectors_per_call': round(total_iters / (args.steps * world), 2),
-                       **({'options': list(args.option)} if args.option else {})},
+        line = headline(args, n, world, comm, tmax, total_iters)
+        line.update({
             'davidson_loop_only_iter_per_s': round(it2 / t_loop, 1),
             'ms_per_vector_loop': round(1e3 * t_loop / max(1, it2), 4),
             'eigh_ms': round(1e3 * t_eigh, 2),
@@ -923,14 +957,10 @@ def main():
             'block_davidson': block_stats,
             'parity': {'lowest_ritz_value': float(lams[0]), 'ritz_residual_norm': resid, 'max_abs_AV_minus_A_V': av_err,
                        'converged_run': conv},
-            'collective': {'kind': comm.kind, 'nranks': getattr(comm, 'nranks', comm.world)},
             'roofline': roof, 'cpu_baseline': cpu,
-        }
+        })
         print(json.dumps(line), flush=True)
-    comm.barrier()
-    comm.close()
-    if comm.kind == 'torch.distributed':
-        comm.dist.destroy_process_group()
+    close_comm(comm)
 
 
 if __name__ == '__main__':

@@ -95,12 +95,13 @@ def ensemble(out_path, n_replicas):
     dist.destroy_process_group()
 
 
-def bench(out_path):
+def bench(out_path, full):
+    """bench.py at toy size on the ranks of this job; `full`: with --full, the legs behind the timed steps too."""
     import io
     from contextlib import redirect_stdout
     import bench as bench_mod
     os.environ['SELLA_BENCH_COMM'] = 'gloo'
-    sys.argv = ['bench.py', '--gpus', os.environ['WORLD_SIZE'], '--steps', '2', '--warmup', '1', '--n', '36', '--option', 'eigh_tail_lds=0',
+    sys.argv = ['bench.py', *(['--full'] if full else []), '--gpus', os.environ['WORLD_SIZE'], '--steps', '2', '--warmup', '1', '--n', '36', '--option', 'eigh_tail_lds=0',
                 '--maxiter', '8', '--seeds', '2', '--converged-n', '0', '--emt-steps', '0', '--no-cpu-baseline', '--opt-steps', '2', '--ensemble-per-gpu', '2', '--ensemble-n', '12', '--ensemble-steps', '2', '--block-n', '70', '--block-iters', '3', '--block-eigh', '0']
     buf = io.StringIO()
     with redirect_stdout(buf):
@@ -153,8 +154,8 @@ if __name__ == '__main__':
         ensemble(sys.argv[2], int(sys.argv[3]))
     elif sys.argv[1] in ('ensemble-cohort', 'ensemble-cohort-serial'):
         ensemble_cohort(sys.argv[2], int(sys.argv[3]), sys.argv[1] == 'ensemble-cohort')
-    elif sys.argv[1] == 'bench':
-        bench(sys.argv[2])
+    elif sys.argv[1] in ('bench', 'bench-plain'):
+        bench(sys.argv[2], full=sys.argv[1] == 'bench')
     elif sys.argv[1] == 'bench-dump':
         bench_dump(sys.argv[2], sys.argv[3], sys.argv[4])
     elif sys.argv[1] == 'panel':

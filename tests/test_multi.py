@@ -116,6 +116,25 @@ def test_bench_two_ranks(tmp_path):
     assert ens['replicas'] == 4 and ens['per_gpu'] == 2 and ens['optimizer_steps_per_s'] > 0
 
 
+# what a plain run of bench.py prints: the headline figure and the run's description, nothing a further leg measures
+PLAIN_LINE_KEYS = {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
+                   'vs_baseline', 'dtype', 'data', 'config', 'collective'}
+
+
+def test_bench_two_ranks_plain(tmp_path):
+    """Without --full the two ranks run the timed steps alone: the line holds the headline fields and no leg's."""
+    out = str(tmp_path / 'bench.json')
+    launch(2, 'bench-plain', out)
+    lines = [ln for ln in open(out).read().splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert set(d) == PLAIN_LINE_KEYS
+    assert d['n_gpus'] == 2 and d['steps'] == 2 and d['warmup'] == 1
+    assert d['scaling'] == 'weak' and d['unit'] == 'davidson_iter/s' and d['higher_is_better'] is True
+    assert d['value'] > 0 and d['ms_per_step'] > 0 and d['dtype'] == 'f64'
+    assert d['collective']['kind'] == 'torch.distributed' and d['collective']['nranks'] == 2
+
+
 def test_bench_dump_outputs(tmp_path):
     """--dump-outputs writes what the last timed step returned; --steps sets which step that is.  Two problems
     (--seeds 2 --starts 1) alternate: step 3 solves step 1's problem again, step 2 the other one."""
@@ -127,6 +146,7 @@ def test_bench_dump_outputs(tmp_path):
         assert len(lines) == 1
         d = json.loads(lines[0])
         assert d['steps'] == steps and d['ms_per_step'] > 0
+        assert set(d) == PLAIN_LINE_KEYS                # (a plain run)
         dumps[tag] = {f[:-4]: np.load(os.path.join(ddir, f)) for f in os.listdir(ddir)}
     for a in dumps.values():
         assert sorted(a) == ['AV', 'V', 'lams', 'nmatvec']

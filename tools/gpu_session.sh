@@ -36,12 +36,12 @@ timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1; say "p
 tail -5 $OUT/pytest_gpu.log | tee -a $OUT/session.log
 fi
 say "== bench"
-timeout 900 python bench.py > $OUT/bench.log 2>&1; say "bench exit $?"
+timeout 900 python bench.py --full > $OUT/bench.log 2>&1; say "bench exit $?"
 tail -1 $OUT/bench.log > $OUT/bench_line.json; cat $OUT/bench_line.json | tee -a $OUT/session.log
 say "== kernel statistics"
 # (the threaded legs — ensemble threads, cohorts' issuing threads, concurrent problems — have crashed rocprofv3's kernel tracing
 #  inside a launch issued from a worker thread, r03D / r05G: the statistics are taken with those legs off)
-prof bench "bench.py --steps 5 --warmup 1 --no-cpu-baseline --ensemble-procs 0 --ensemble-threads 0 --concurrent 1 (rocprofv3 --kernel-trace --stats)" python $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --ensemble-procs 0 --ensemble-threads 0 --concurrent 1
+prof bench "bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --ensemble-procs 0 --ensemble-threads 0 --concurrent 1 (rocprofv3 --kernel-trace --stats)" python $R/bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --ensemble-procs 0 --ensemble-threads 0 --concurrent 1
 prof eigh "tools/eigh_only.py 3072 4 (rocprofv3 --kernel-trace --stats)" python $R/tools/eigh_only.py 3072 4
 prof davidson_loop "tools/dav_time.py (rocprofv3 --kernel-trace --stats)" python $R/tools/dav_time.py
 prof block_iter "tools/block_iter.py 12288 12 (rocprofv3 --kernel-trace --stats)" python $R/tools/block_iter.py 12288 12
