@@ -52,41 +52,17 @@ int sella_ctx_create(int device, sella_ctx** ctx);
 int sella_ctx_destroy(sella_ctx* ctx);
 int sella_ctx_sync(sella_ctx* ctx);
 int sella_ctx_device_name(sella_ctx* ctx, char* buf, int buflen);
-/* integer tuning knobs (kernel variant selection for benchmarking); unknown key -> error.  Keys (defaults):
- *   gemv_rw (0 = by size) rows per workgroup of the streaming matvec | gemm_mfma (1) GEMMs on the matrix cores |
- *   gemm_tile128 (1) 128x128 GEMM tiles for large products | panel_mfma (1), panel_rows (0 = by size) the
- *   H.V block product | host_scalars (0) zero-copy scalars | rank2k_stream (1) mirror-free trailing update |
- *   eigh_nb (16) panel width, eigh_leaf (16) leaf size, eigh_wy_mfma (1) MFMA back-transformation |
- *   eigh_symv_min (5120) trailing blocks of the tridiagonalisation with at least this many rows take the
- *   symmetric-aware matvec (upper triangle only, fixed-order partial sums; 0: never), eigh_symv_tr (64) rows per tile
- *   of it, eigh_symv_tri (1) trailing update on the upper triangle only while it runs | eigh_wy_nb64_min (2560) 64
- *   instead of 32 reflectors per block of the back-transformation from this many rows on |
- *   dav_fuse_scale (1), dav_zero_copy (0) Davidson chain: diagonal scaling inside the residual kernel, coefficients read
- *   from pinned host memory |
- *   eigh_tail_lds (128) the last <= 128 columns of the tridiagonalisation inside one workgroup, the block in LDS |
- *   rs_batch (1) bisection phase of sella_restricted_step: 15 trial alphas per device round trip |
- *   panel_small (2048) panel products with <= 64 rows and <= 16 right-hand sides take the split-K kernels from this
- *   many columns on | bd_pipeline (1) sella_davidson_block as a pipelined iteration: projection and block Gram
- *   matrix from one panel product, two polled waits per iteration (0: the general loop) | bd_early_matvec (1) ... with A applied
- *   to the raw correction block while the host orthonormalises it (error budget for the transformed A T) | lr_dev (1) sella_opt_step updates structured eigendecompositions in
- *   coordinates with every decision on the device (0: the host-planned rank-one merges of sella_update_h_lr) |
- *   eigh_wy_waves (4), eigh_wy_rows (16) wavefronts / rows of X per workgroup of the back-transformation (8, 16 / 32
- *   measured equal or slower) | rank2k_fixed (1) trailing update with all loads up front | lr_cholqr (1) block of update
- *   vectors by rank-revealing Cholesky-QR |
- *   rs_fast (1) sella_opt_step finds the restricted step by interpolating batches of 15 trial alphas instead of the
- *   reference's Newton / bisection schedule (same root) |
- *   eigh_upd_max (1024): trailing blocks of the tridiagonalisation with at most this many rows take ONE launch per column
- *   (the block kept up to date by the launch itself; 0: the blocked two-launch chain throughout), eigh_upd_rows (0 = 2),
- *   eigh_upd_nt (512) rows / most threads per workgroup of that launch | eigh_gemv_flat (1) trailing matvec of the blocked
- *   chain with every load issued before the first wait (0: the loop form; same sums, bit for bit), eigh_dc_pipeline (1)
- *   divide & conquer with ONE host wait per level (0: two; same results bit for bit), eigh_wy_overlap (1) compact-WY
- *   factors on a second stream beside divide & conquer | h2d_kernel_min (16384) host-to-device payloads of at least this
- *   many bytes are copied by a kernel that reads the pinned staging ring (0: always the runtime's copy) |
- *   lr_chain (1) the structured quasi-Newton update of sella_opt_step as the fused launch chain of round 4 (0: round 3's
- *   kernels), lr_pipe (1) the force call queued in front of the update that consumes it, rs_batch_result (1) final step
- *   read from the batch of trial alphas that produced it, lr_overlap (0) view job on a second stream |
- *   emt_hcap (8) neighbour-list slots per thread of the EMT kernels (1 .. 8; tests lower it to reach the overflow path). */
+/* Integer tuning options of a context (kernel variant selection for benchmarking and tests).  The list — name, default,
+ * accepted values, the measurements behind each default — is sella_amd/csrc/options.h and only that file.  set_option
+ * applies the option's rule to the value (booleans normalised to 0 / 1, sizes clamped or rejected) and stores it,
+ * get_option reads it back, sella_option_name enumerates the names (index 0, 1, ...; NULL past the end; no context
+ * needed).  An unknown key or a rejected value returns SELLA_E_INVALID with the reason in sella_last_error() and changes
+ * nothing.  Nothing but set_option changes an option, so a value read with get_option and set again later restores it.
+ * What callers rely on: eigh_gemv_flat and eigh_dc_pipeline choose between forms that give the same results bit for
+ * bit; rs_fast finds the same root as the reference's Newton / bisection schedule; emt_hcap is meaningful from 1 to 8. */
 int sella_ctx_set_option(sella_ctx* ctx, const char* key, long value);
+int sella_ctx_get_option(sella_ctx* ctx, const char* key, long* value);
+const char* sella_option_name(int index);
 
 /* ---- device matrices --------------------------------------------------------------- */
 /* to_gpu(A): sella/_gpu.py:55-67 (upload, cached by ApproximateHessian linalg.py:197-207) */

@@ -17,6 +17,7 @@ _lib = None
 
 c_double_p = POINTER(c_double)
 c_int_p = POINTER(c_int)
+c_long_p = POINTER(c_long)
 MATVEC_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_double_p, c_double_p, c_int)
 ALLGATHER_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p)
 
@@ -62,6 +63,8 @@ SIGNATURES = {
     'sella_ctx_sync': (c_int, [c_void_p]),
     'sella_ctx_device_name': (c_int, [c_void_p, c_char_p, c_int]),
     'sella_ctx_set_option': (c_int, [c_void_p, c_char_p, c_long]),
+    'sella_ctx_get_option': (c_int, [c_void_p, c_char_p, c_long_p]),
+    'sella_option_name': (c_char_p, [c_int]),
     'sella_mat_upload': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int_p]),
     'sella_mat_alloc': (c_int, [c_void_p, c_int, c_int, c_int_p]),
     'sella_mat_set': (c_int, [c_void_p, c_int, c_void_p]),

@@ -1,6 +1,8 @@
 // context.hip — context, device matrices, scratch pool, profiling hooks and the simple
 // C-ABI entry points (uploads, products, projection).  See include/sella_hip.h.
 #include "internal.h"
+#include <algorithm>
+#include <climits>
 
 namespace sella {
 
@@ -483,10 +485,10 @@ int host_stage(sella_ctx* c, size_t bytes, void** p) {
     return SELLA_OK;
 }
 
-double* scal_out(sella_ctx* c, int offset) { return (c->opt.host_scalars ? c->hscal : c->dscal) + offset; }
+double* scal_out(sella_ctx* c, int offset) { return (host_scalars(c) ? c->hscal : c->dscal) + offset; }
 
 int sync_scalars(sella_ctx* c, int offset, int count) {
-    if (!c->opt.host_scalars) return read_scalars(c, offset, count);
+    if (!host_scalars(c)) return read_scalars(c, offset, count);
     SCHK(stream_wait(c));
     return SELLA_OK;
 }
@@ -634,84 +636,60 @@ int sella_ctx_device_name(sella_ctx* c, char* buf, int buflen) {
     return SELLA_OK;
 }
 
+// ---- options: one table, generated from options.h --------------------------------------
+namespace {
+struct OptionRule { char kind; int n; long v[5]; };           // v: [lo, hi] of a clamp / range, the values of a one-of
+#define OPT_BOOL {'b', 0, {}}
+#define OPT_ANY {'a', 0, {}}
+#define OPT_CLAMP(lo, hi) {'c', 2, {lo, hi}}
+#define OPT_FLOOR0 OPT_CLAMP(0, LONG_MAX)
+#define OPT_RANGE(lo, hi) {'r', 2, {lo, hi}}
+#define OPT_ONEOF(...) {'o', (int)std::initializer_list<long>{__VA_ARGS__}.size(), {__VA_ARGS__}}
+const struct OptionDef { const char* name; long sella::Options::*field; OptionRule rule; } option_table[] = {
+#define SELLA_OPTION(name, dflt, rule) {#name, &sella::Options::name, rule},
+#include "options.h"
+#undef SELLA_OPTION
+};
+
+const OptionDef* find_option(const char* key) {
+    for (const OptionDef& d : option_table)
+        if (!strcmp(d.name, key)) return &d;
+    set_error("unknown option '%s'", key);
+    return nullptr;
+}
+}  // namespace
+
+const char* sella_option_name(int index) {
+    return index >= 0 && index < (int)(sizeof(option_table) / sizeof(*option_table)) ? option_table[index].name : nullptr;
+}
+
+int sella_ctx_get_option(sella_ctx* c, const char* key, long* value) {
+    const OptionDef* d = c && key && value ? find_option(key) : nullptr;
+    if (!d) return SELLA_E_INVALID;
+    *value = c->opt.*(d->field);
+    return SELLA_OK;
+}
+
 int sella_ctx_set_option(sella_ctx* c, const char* key, long value) {
-    if (!c || !key) return SELLA_E_INVALID;
-    if (!strcmp(key, "gemv_rw")) {
-        if (value != 0 && value != 1 && value != 2 && value != 4) { set_error("gemv_rw must be 0, 1, 2 or 4"); return SELLA_E_INVALID; }
-        c->opt.gemv_rw = value;
-    } else if (!strcmp(key, "gemm_mfma")) c->opt.gemm_mfma = value ? 1 : 0;
-    else if (!strcmp(key, "rank2k_stream")) c->opt.rank2k_stream = value ? 1 : 0;
-    else if (!strcmp(key, "eigh_wy_rows")) c->opt.eigh_wy_rows = value;
-    else if (!strcmp(key, "eigh_wy_nb64_min")) c->opt.eigh_wy_nb64_min = value;
-    else if (!strcmp(key, "dav_fuse_scale")) c->opt.dav_fuse_scale = value ? 1 : 0;
-    else if (!strcmp(key, "dav_zero_copy")) c->opt.dav_zero_copy = value ? 1 : 0;
-    else if (!strcmp(key, "dav_poll")) c->opt.dav_poll = value ? 1 : 0;
-    else if (!strcmp(key, "rs_poll")) c->opt.rs_poll = value ? 1 : 0;
-    else if (!strcmp(key, "rs_hint")) c->opt.rs_hint = value ? 1 : 0;
-    else if (!strcmp(key, "eigh_tail_lds")) c->opt.eigh_tail_lds = value < 0 ? 0 : value;
-    else if (!strcmp(key, "eigh_wy_waves")) c->opt.eigh_wy_waves = value;
-    else if (!strcmp(key, "lr_cholqr")) c->opt.lr_cholqr = value ? 1 : 0;
-    else if (!strcmp(key, "rank2k_fixed")) c->opt.rank2k_fixed = value ? 1 : 0;
-    else if (!strcmp(key, "eigh_wy_strip")) c->opt.eigh_wy_strip = value;
-    else if (!strcmp(key, "gs_small")) c->opt.gs_small = value < 0 ? 0 : (value > 2048 ? 2048 : value);
-    else if (!strcmp(key, "h2d_kernel_min")) c->opt.h2d_kernel_min = value < 0 ? 0 : value;
-    else if (!strcmp(key, "eigh_dc_pipeline")) c->opt.eigh_dc_pipeline = value ? 1 : 0;
-    else if (!strcmp(key, "eigh_gemv_flat")) c->opt.eigh_gemv_flat = value ? 1 : 0;
-    else if (!strcmp(key, "lr_dev")) c->opt.lr_dev = value ? 1 : 0;
-    else if (!strcmp(key, "lr_chain")) c->opt.lr_chain = value ? 1 : 0;
-    else if (!strcmp(key, "lr_pipe")) c->opt.lr_pipe = value ? 1 : 0;
-    else if (!strcmp(key, "eigh_wy_overlap")) c->opt.eigh_wy_overlap = value ? 1 : 0;
-    // (one launch per column: at most 1024 workgroups of at most 8 rows, eigh.hip TRD_UPD_MAXGRID — larger blocks stay
-    //  with the blocked chain instead of failing in the middle of a factorisation)
-    else if (!strcmp(key, "eigh_upd_max")) c->opt.eigh_upd_max = value < 0 ? 0 : (value > 8 * 1024 - 64 ? 8 * 1024 - 64 : value);
-    else if (!strcmp(key, "eigh_upd_rows")) {
-        if (value != 0 && value != 2 && value != 4 && value != 8) { set_error("eigh_upd_rows must be 0, 2, 4 or 8"); return SELLA_E_INVALID; }
-        c->opt.eigh_upd_rows = value;
-    }
-    else if (!strcmp(key, "eigh_upd_nt")) {
-        if (value != 128 && value != 256 && value != 512) { set_error("eigh_upd_nt must be 128, 256 or 512"); return SELLA_E_INVALID; }
-        c->opt.eigh_upd_nt = value;
-    }
-    else if (!strcmp(key, "eigh_upd_r4_min")) c->opt.eigh_upd_r4_min = value < 0 ? 0 : value;
-    else if (!strcmp(key, "eigh_upd_r8_min")) c->opt.eigh_upd_r8_min = value < 0 ? 0 : value;
-    else if (!strcmp(key, "emt_hcap")) c->opt.emt_hcap = value;
-    else if (!strcmp(key, "lr_overlap")) c->opt.lr_overlap = value ? 1 : 0;
-    else if (!strcmp(key, "rs_batch_result")) c->opt.rs_batch_result = value ? 1 : 0;
-    else if (!strcmp(key, "rs_fast")) c->opt.rs_fast = value ? 1 : 0;
-    else if (!strcmp(key, "rs_batch")) c->opt.rs_batch = value ? 1 : 0;
-    else if (!strcmp(key, "bd_pipeline")) c->opt.bd_pipeline = value ? 1 : 0;
-    else if (!strcmp(key, "bd_early_matvec")) c->opt.bd_early_matvec = value ? 1 : 0;
-    else if (!strcmp(key, "dav_rotate_fused")) c->opt.dav_rotate_fused = value ? 1 : 0;
-    else if (!strcmp(key, "panel_small")) c->opt.panel_small = value > 0 ? value : 0;
-    else if (!strcmp(key, "eigh_leaf")) {
-        if (value < 2 || value > 64) { set_error("eigh_leaf must be in [2, 64]"); return SELLA_E_INVALID; }
-        c->opt.eigh_leaf = value;
-    } else if (!strcmp(key, "host_scalars")) {
-        c->opt.host_scalars = value ? 1 : 0;
-    } else if (!strcmp(key, "gemm_tile128")) {
-        c->opt.gemm_tile128 = value ? 1 : 0;
-    } else if (!strcmp(key, "panel_mfma")) {
-        c->opt.panel_mfma = value ? 1 : 0;
-    } else if (!strcmp(key, "panel_rows")) {
-        if (value != 0 && value != 16 && value != 32 && value != 48 && value != 64) { set_error("panel_rows must be 0, 16, 32, 48 or 64"); return SELLA_E_INVALID; }
-        c->opt.panel_rows = value;
-    } else if (!strcmp(key, "eigh_wy_mfma")) {
-        c->opt.eigh_wy_mfma = value ? 1 : 0;
-    } else if (!strcmp(key, "eigh_symv_tri")) {
-        c->opt.eigh_symv_tri = value ? 1 : 0;
-    } else if (!strcmp(key, "eigh_symv_tr")) {
-        if (value != 64 && value != 128) { set_error("eigh_symv_tr must be 64 or 128"); return SELLA_E_INVALID; }
-        c->opt.eigh_symv_tr = value;
-    } else if (!strcmp(key, "eigh_symv_min")) {
-        if (value < 0) { set_error("eigh_symv_min must be >= 0"); return SELLA_E_INVALID; }
-        c->opt.eigh_symv_min = value;
-    } else if (!strcmp(key, "eigh_nb")) {
-        if (value < 1 || value > 64) { set_error("eigh_nb must be in [1, 64]"); return SELLA_E_INVALID; }
-        c->opt.eigh_nb = value;
-    } else {
-        set_error("unknown option '%s'", key);
+    const OptionDef* d = c && key ? find_option(key) : nullptr;
+    if (!d) return SELLA_E_INVALID;
+    const OptionRule& r = d->rule;
+    switch (r.kind) {
+    case 'b': value = value ? 1 : 0; break;
+    case 'c': value = std::min(std::max(value, r.v[0]), r.v[1]); break;
+    case 'r':
+        if (value >= r.v[0] && value <= r.v[1]) break;
+        set_error("%s must be in [%ld, %ld]", key, r.v[0], r.v[1]);
+        return SELLA_E_INVALID;
+    case 'o': {
+        if (std::find(r.v, r.v + r.n, value) != r.v + r.n) break;
+        char list[128];
+        for (int i = 0, len = 0; i < r.n; ++i) len += snprintf(list + len, sizeof(list) - len, i ? ", %ld" : "%ld", r.v[i]);
+        set_error("%s must be one of %s", key, list);
         return SELLA_E_INVALID;
     }
+    }
+    c->opt.*(d->field) = value;
     return SELLA_OK;
 }
 

@@ -789,12 +789,12 @@ extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec
     s.qt_mode = s.A != nullptr && s.Q != nullptr && s.prank == n && method >= SELLA_DAV_GD && method <= SELLA_DAV_JD0_ALT &&
                 vref == nullptr && !getenv("SELLA_DAV_SYNC") && !getenv("SELLA_DAV_NOQT");
     // Polled waits (dav_poll) read the iteration's scalars where its kernels stored them — in the pinned mirror: the fused
-    // iteration then runs with host-visible scalars for the length of this call (restored on every way out).
+    // iteration then runs with host-visible scalars for the length of this call (released on every way out).
     struct HostScalarsScope {
-        sella_ctx* c; long saved;
-        ~HostScalarsScope() { c->opt.host_scalars = saved; }
-    } hs_scope{c, c->opt.host_scalars};
-    if (s.qt_mode && c->opt.dav_poll) c->opt.host_scalars = 1;
+        sella_ctx* c; int held;
+        ~HostScalarsScope() { c->hscal_hold -= held; }
+    } hs_scope{c, s.qt_mode && c->opt.dav_poll ? 1 : 0};
+    c->hscal_hold += hs_scope.held;
     if (maxiter <= 0) maxiter = 2 * n + 1;
     const int kstop = (n < maxiter) ? n : maxiter;
 
@@ -823,7 +823,7 @@ extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec
             if (nv0 == 1) DCHK(h2d_async(c, slot, v0, (size_t)n * sizeof(double)));          // (one start vector: straight into its slot)
             else DHIP(s_memcpy(c, slot, tmp + (size_t)j * s.ld, (size_t)s.ld * sizeof(double), hipMemcpyDeviceToDevice));
             int kept = 0;
-            if (nv0 == 1 && c->opt.host_scalars && !(c->opt.gs_small && n <= c->opt.gs_small) && !(c->cohort && cohort_in_fiber())) {
+            if (nv0 == 1 && host_scalars(c) && !(c->opt.gs_small && n <= c->opt.gs_small) && !(c->cohort && cohort_in_fiber())) {
                 // one start vector, scalars in the pinned mirror: its normalisation and its product A v are queued together
                 // and waited for ONCE (the norms of the sweeps are read behind append_vector's wait) — the decision below is
                 // gs_orthonormalise's for an empty basis; a vector that fails it leaves through the error exit as before
@@ -1069,7 +1069,7 @@ extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec
         auto launch_resid = [&]() -> int {
             double* dC;
             const int ncoef = (2 * nneg + 1) * k;
-            if (c->opt.host_scalars && ncoef <= 8192) {
+            if (host_scalars(c) && ncoef <= 8192) {
                 // zero-copy: the kernels stage the coefficients into LDS straight from pinned host memory (one
                 // coalesced read over PCIe instead of a copy launch on the chain); the slot is rewritten only after
                 // this iteration's synchronisation
@@ -1164,7 +1164,7 @@ extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec
             SELLA_LAUNCHB(c, dav_gs2_kernel, dav_gs2_vb, 256, dim3(nblk), dim3(256), 0, n, k, s.Vp, s.AVp, s.ld, t1, At1, c2d, part,
                                nblk, t2, At2, part + 2 * DF_MAXBLK);
             // (polled wait: the kernel's last workgroup publishes the sequence word itself)
-            const bool poll = s.qt_mode && c->opt.dav_poll && c->opt.host_scalars;
+            const bool poll = s.qt_mode && c->opt.dav_poll && host_scalars(c);
             unsigned long long* pword = nullptr;
             unsigned long long pseq = 0;
             unsigned* pcount = nullptr;
@@ -1178,7 +1178,7 @@ extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec
                 // and there is nothing to copy), mark that point, queue the eigenbasis images of the new vector behind it
                 // (they run while the host decides and does the next Rayleigh-Ritz step), wait for the mark only
                 const int cnt = (int)(S0 + 8 + nneg);
-                if (!c->opt.host_scalars)
+                if (!host_scalars(c))
                     DHIP(s_memcpy(c, c->hscal + DS_GRAM, c->dscal + DS_GRAM, (size_t)cnt * sizeof(double), hipMemcpyDeviceToHost, true));
                 if (!poll) {
                     if (!s.ev) DHIP(hipEventCreate(&s.ev));

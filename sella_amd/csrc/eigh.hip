@@ -2470,7 +2470,7 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
     }
     const int tail_lds = (int)std::min<long>(c->opt.eigh_tail_lds, TRD_TAIL);
     bool lower_stale = false;                          // the trailing update has been writing the upper triangle only
-    const bool can_tri = c->opt.rank2k_stream && c->opt.eigh_symv_tri;
+    const bool can_tri = c->opt.rank2k_stream;
     for (int j0 = 0; j0 < nrefl; j0 += nb) {
         const int kb = std::min(nb, nrefl - j0);
         if (upd_max > 0 && !lower_stale && n - j0 - 1 <= upd_max && !(tail_lds > 0 && n - j0 <= tail_lds) &&
@@ -2489,7 +2489,7 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
                 ua.colscal_prev = colscal2[1 - fc]; ua.colscal_cur = colscal2[fc];
                 ua.taus = taus; ua.evec = evec; ua.dvec = dvec;
                 int R = (int)c->opt.eigh_upd_rows;
-                if (R != 2 && R != 4 && R != 8) R = m >= c->opt.eigh_upd_r8_min ? 8 : m >= c->opt.eigh_upd_r4_min ? 4 : 2;
+                if (R != 2 && R != 4 && R != 8) R = 2;
                 while (R < 8 && (8 * R + m + R - 1) / R > TRD_UPD_MAXGRID) R *= 2;
                 ua.pad = o % (8 * R);
                 const int grid = (ua.pad + m + R - 1) / R;

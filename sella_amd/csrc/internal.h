@@ -102,71 +102,11 @@ struct ProfSlot {
     double ms = 0, bytes = 0, flops = 0;
 };
 
+// the tuning options of a context, written by sella_ctx_set_option only: options.h is the list
 struct Options {
-    long gemv_rw = 0;        // rows per workgroup in the row-panel matvec (1, 2, 4; 0 = by size: 4 from 4096 rows on, else 2)
-    long gemm_mfma = 1;      // 1: MFMA f64 16x16x4 GEMM tiles, 0: VALU register tiles
-    long host_scalars = 0;   // 1: host-consumed scalars are written straight into pinned host memory (measured: no gain)
-    long gemm_tile128 = 1;   // 1: 128x128 double-buffered tiles for large NN/TN products
-    long eigh_leaf = 16;     // leaf size of the divide-and-conquer tree (16: 39.7 ms per eigh at n = 3072, 32: 40.2, 64: 41.5)
-    long eigh_symv_tri = 1;      // ... and the trailing update then writes the upper triangle only (mirrored once, when the
-                                 // trailing block drops below eigh_symv_min)
-    long eigh_symv_tr = 64;      // rows per tile of that matvec (64 or 128)
-    long eigh_symv_min = 5120;   // trailing blocks of at least this many rows use the symmetric-aware matvec of the
-                                 // tridiagonalisation (upper triangle only, eigh.hip); 0: never
-    long eigh_nb = 16;       // panel width of the blocked tridiagonalisation (tools/eigh_tune.py)
-    long panel_mfma = 1;     // 1: products with more than 8 right-hand sides stream the matrix once (MFMA panel kernel)
-    long panel_rows = 0;     // rows per workgroup of the panel kernel: 16, 32, 48, 64, or 0 = by size (one workgroup per CU)
-    long eigh_wy_mfma = 1;   // 1: back-transformation on the matrix cores, 0: VALU/LDS variant
-    long dav_fuse_scale = 1;     // Davidson chain: (d - theta)^-1 scaling in the epilogue of the residual kernel (0: own kernel)
-    long dav_poll = 1;           // ... 1: the fused iteration's one wait polls a sequence word in pinned host memory, written by a
-                                 //    one-thread kernel behind the iteration's last kernel (the scalars of the iteration are then
-                                 //    stored there by their kernels for the length of the call), instead of sleeping on an event — the wake-up of an interrupt-driven wait is
-                                 //    ~10 us of a ~95 us iteration
-    long dav_zero_copy = 0;      // ... its coefficients read from pinned host memory instead of a copy launch (measured equal or slower)
-    long eigh_tail_lds = 128;    // trailing blocks of at most this many rows (<= 128) are tridiagonalised by one workgroup in LDS (0: never)
-    long eigh_wy_nb64_min = 2560; // 64 instead of 32 reflectors per block of the back-transformation from this many rows on (0: never)
-    long eigh_wy_rows = 16;  // rows of X per workgroup of the MFMA back-transformation (16, or 32: two row tiles)
-    long eigh_wy_waves = 4;  // wavefronts per workgroup of the MFMA back-transformation (4, 8 or 16: measured equal at n = 3072 and 12288 — the kernel is bound by L2 bandwidth, 22.7 GB in 3.16 ms, not by latency)
-    long lr_cholqr = 1;      // 1: block of update vectors orthonormalised by Cholesky-QR twice (eigh.hip, lr_lowrank_update)
-    long h2d_kernel_min = 16384; // host-to-device payloads of at least this many bytes are copied by a kernel reading the pinned ring (0: never)
-    long eigh_dc_pipeline = 1; // 1: divide & conquer queues the next level's rank-one vectors behind the current level (one wait per level)
-    long eigh_gemv_flat = 1; // 1: trailing matvec of the tridiagonalisation with every load issued before the first wait (eigh.hip)
-    long eigh_wy_strip = 1;  // 1: back-transformation with the strip of X in registers for the whole sweep (n = ld a multiple of 64,
-                             //    2048 < n <= 3072: 2.49 -> 2.19 ms, L2 traffic 19.9 -> 14.5 GB); 2: any such n <= 3072 (tests); 0: never
-    long rank2k_fixed = 1;   // 1: trailing update with all loads issued up front for the panel depths 16 / 32 (update.hip)
-    long rs_fast = 1;        // 1: sella_opt_step searches the restricted step by interpolating batches (stepper.hip)
-    long lr_dev = 1;         // 1: sella_opt_step updates structured decompositions in coordinates, all decisions on the device (lrstep.hip)
-    long rank2k_stream = 1;  // 1: trailing update of the tridiagonalisation as a mirror-free MFMA stream (update.hip)
-    long panel_small = 2048; // panel products with <= 64 rows and at least this many columns split the long index over the
-                             // chip (kernels.hip); 0: never
-    long dav_rotate_fused = 1; // sella_davidson's result stage: rotation into the Ritz basis and the caller's layout in one launch (k <= 32)
-    long bd_early_matvec = 1; // pipelined block Davidson: 1 = A applied to the raw correction block while the host orthonormalises it
-                             // (A T by the same coefficients as T, error budget; see davidson_block.hip), 0 = A applied to the final T
-    long bd_pipeline = 1;    // block Davidson: pipelined iteration (davidson_block.hip run_pipelined: A applied to the raw correction
-                             // block while the host does the SVQB step, two polled waits per iteration); 0: the general loop
-    long eigh_wy_overlap = 1; // 1: Gram matrices / triangular factors of the compact-WY blocks on a second stream, beside divide & conquer
-    long eigh_upd_max = 1024; // trailing blocks of at most this many rows are tridiagonalised with ONE launch per column, the block
-                             //    kept up to date by the launch itself (trd_upd_kernel, eigh.hip); 0: never.  eigh at n = 3072 by
-                             //    switch-over size (session r05b): 0: 39.85 ms, 512: 38.78, 1024: 38.28, 1536: 39.07, 2048: 40.19,
-                             //    3072: 47.9 — the block is written back once per column, which only pays while it is small
-    long eigh_upd_rows = 0;  // rows per workgroup of that kernel (2, 4, 8); 0: by trailing size, thresholds below
-    long eigh_upd_nt = 512;  // most threads per workgroup of that kernel (128, 256, 512; tests force several chunks per thread with 128)
-    long eigh_upd_r4_min = 1 << 30, eigh_upd_r8_min = 1 << 30;   // (2 rows per workgroup measured best at every size up to 1024)
-    long emt_hcap = 8;       // neighbour-list slots per thread of the EMT kernels (tests: 1 forces the overflow path)
-    long lr_overlap = 0;     // 1: the view job of the one-call step is queued on a second stream, beside the coordinate kernels of the
-                             //    full-space job.  Measured (session r04k): EMT-slab step 0.59-0.62 ms either way, and the ensemble of EMT
-                             //    members DROPS from 211 to 172-182 searches/s with 8 threads x 2 streams: off
-    long rs_batch_result = 1; // 1: on an expected boundary step the start value rides in the first batch and the final step is read from the
-                              //    batch that produced it (stepper.hip)
-    long lr_pipe = 1;        // 1: the library search queues the force call in front of the update that consumes it: one wait for both (search.hip)
-    long lr_chain = 1;       // 1: the O(n r) passes of the one-call step as five fused launches, merged coordinate kernels (lrstep.hip)
-    long rs_hint = 1;        // 1: the batched root search interpolates quadratically through three evaluated points and, given the alpha the
-                             //    previous root search of the same saddle search ended at (sella_opt_step_t::alpha_hint), looks around it first:
-                             //    4.9 -> 3.5 rounds per boundary step on the EMT slab
-    long rs_poll = 0;        // 1: the rounds of the batched root search wait by polling a pinned sequence word (context.hip, poll_wait); measured equal on the EMT slab (0.576 vs 0.577 ms per step: the mark kernel costs what the wake-up saves): off
-    long gs_small = 2048;    // Gram-Schmidt of vectors of at most this many entries (<= 2048) in ONE launch of one workgroup, sweeps,
-                             //    norms and accept / drop decisions included (gs.hip); 0: always the sweep-by-sweep launches
-    long rs_batch = 1;       // 1: bisection phase of the restricted-step root find evaluates 15 trial alphas per round trip (stepper.hip)
+#define SELLA_OPTION(name, dflt, rule) long name = dflt;
+#include "options.h"
+#undef SELLA_OPTION
 };
 
 }  // namespace sella
@@ -191,6 +131,7 @@ struct sella_ctx {
     double* dscal = nullptr;
     double* hscal = nullptr;
     int nscal = 0;
+    int hscal_hold = 0;             // running calls that need host-visible scalars for their own length (host_scalars())
     // Device allocator: blocks are carved out of a few large arenas and recycled through per-size free
     // lists.  A single hipMalloc was measured at 40-80 ms on this stack whenever the driver has to map new
     // memory, and hipFree synchronises the device; an optimizer loop (or every new member of an ensemble)
@@ -302,9 +243,11 @@ int poll_mark(sella_ctx* c);
 int poll_arm(sella_ctx* c, unsigned long long** word, unsigned long long* seq, unsigned** count);
 int poll_wait(sella_ctx* c);                        // wait for an event recorded on the context's stream
 int read_scalars(sella_ctx* c, int offset, int count);             // dscal -> hscal (sync)
-// Where a kernel should put scalars that only the HOST consumes next: with `host_scalars` on, the pinned,
+// Where a kernel should put scalars that only the HOST consumes next: with host_scalars(c) — the option,
+// or a call that holds it on for its own length (sella_davidson's polled waits) — the pinned,
 // device-visible host mirror itself (zero-copy: the readback is then just the stream synchronisation and the
 // 4 us copy launch disappears from the critical path); otherwise the device buffer.
+inline bool host_scalars(const sella_ctx* c) { return c->opt.host_scalars || c->hscal_hold > 0; }
 double* scal_out(sella_ctx* c, int offset);
 int sync_scalars(sella_ctx* c, int offset, int count);             // makes hscal[offset, offset+count) valid
 // layout of the scalar exchange buffer (doubles)

@@ -2,6 +2,7 @@
 handles.  numpy in / numpy out, fp64, like the reference's accelerator seam
 (sella/_gpu.py:55-132) — but the device side is libsella_hip, not torch.
 """
+import contextlib
 import ctypes
 import os
 import threading
@@ -120,6 +121,32 @@ class Context:
 
     def set_option(self, key, value):
         check(_lib.lib().sella_ctx_set_option(self._h, key.encode(), int(value)))
+
+    def get_option(self, key):
+        v = c_long(0)
+        check(_lib.lib().sella_ctx_get_option(self._h, key.encode(), byref(v)))
+        return v.value
+
+    @staticmethod
+    def option_names():
+        """Names of all options (sella_amd/csrc/options.h is the list)."""
+        names = []
+        while (name := _lib.lib().sella_option_name(len(names))) is not None:
+            names.append(name.decode())
+        return names
+
+    @contextlib.contextmanager
+    def options(self, **values):
+        """`with ctx.options(eigh_nb=8, rs_batch=0): ...` sets the given options for the body and puts back what it
+        found on entry (not the defaults), also when the body raises or a value is rejected."""
+        found = {key: self.get_option(key) for key in values}
+        try:
+            for key, value in values.items():
+                self.set_option(key, value)
+            yield self
+        finally:
+            for key, value in found.items():
+                self.set_option(key, value)
 
     # ---- matrices ---------------------------------------------------------------------
     def upload(self, A):

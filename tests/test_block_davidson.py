@@ -80,11 +80,8 @@ def test_block_davidson_split_panel_products(ctx):
     w, Q, Qt = ctx.eigh(dP)
     outs = {}
     for flag in (64, 0):
-        ctx.set_option('panel_small', flag)
-        try:
+        with ctx.options(panel_small=flag):
             outs[flag] = ctx.davidson_block(dA, n, nev, block=8, tol=1e-9, maxiter=200, maxvec=32, Pvecs=Q, PvecsT=Qt, pevals=w)
-        finally:
-            ctx.set_option('panel_small', 2048)
         check_pairs(A, outs[flag], nev)
     np.testing.assert_allclose(outs[64]['lams'], outs[0]['lams'], atol=1e-11)
     assert outs[64]['niter'] == outs[0]['niter']
@@ -110,11 +107,8 @@ def test_block_davidson_pipelined_against_general_loop(ctx, precond):
         kw = dict(diag=np.diag(A).copy())
     outs = {}
     for flag in (1, 0):
-        ctx.set_option('bd_pipeline', flag)
-        try:
+        with ctx.options(bd_pipeline=flag):
             outs[flag] = ctx.davidson_block(dA, n, nev, block=16, tol=1e-8, maxiter=400, **kw)
-        finally:
-            ctx.set_option('bd_pipeline', 1)
         check_pairs(A, outs[flag], nev)
     np.testing.assert_allclose(outs[1]['lams'], outs[0]['lams'], atol=1e-10)
 
@@ -130,11 +124,8 @@ def test_block_davidson_pipelined_random_start_block(ctx, seed, early):
     A = np.diag(np.arange(1, n + 1) * 0.5) + 0.02 * (N + N.T)
     dA = ctx.upload(A)
     V0 = np.random.RandomState(seed).normal(size=(n, 7))
-    ctx.set_option('bd_early_matvec', early)
-    try:
+    with ctx.options(bd_early_matvec=early):
         out = ctx.davidson_block(dA, n, 5, block=16, tol=1e-9, maxiter=200, V0=V0, diag=np.diag(A).copy())
-    finally:
-        ctx.set_option('bd_early_matvec', 1)
     check_pairs(A, out, 5)
     assert out['niter'] < 120          # (84 - 91 in the general loop; 71 - 77 here since the restart keeps 2 nev vectors)
 
@@ -149,11 +140,8 @@ def test_block_davidson_early_matrix_pass(ctx):
     dA = ctx.upload(A)
     outs = {}
     for flag in (1, 0):
-        ctx.set_option('bd_early_matvec', flag)
-        try:
+        with ctx.options(bd_early_matvec=flag):
             outs[flag] = ctx.davidson_block(dA, n, nev, block=16, tol=1e-9, maxiter=400, diag=np.diag(A).copy())
-        finally:
-            ctx.set_option('bd_early_matvec', 1)
         check_pairs(A, outs[flag], nev)
     np.testing.assert_allclose(outs[1]['lams'], outs[0]['lams'], atol=1e-10)
 

@@ -18,13 +18,13 @@ def test_symm_mm(ctx):
         dA = ctx.upload(A)
         ref = A @ X
         for rw in (1, 2, 4):
-            ctx.set_option('gemv_rw', rw)
-            np.testing.assert_allclose(ctx.symm_mm(dA, X), ref, atol=1e-13 * n * np.abs(ref).max())
-        np.testing.assert_allclose(ctx.symm_mm(dA, X[:, 0]), ref[:, 0], atol=1e-13 * n * np.abs(ref).max())
+            with ctx.options(gemv_rw=rw):
+                np.testing.assert_allclose(ctx.symm_mm(dA, X), ref, atol=1e-13 * n * np.abs(ref).max())
+        with ctx.options(gemv_rw=4):
+            np.testing.assert_allclose(ctx.symm_mm(dA, X[:, 0]), ref[:, 0], atol=1e-13 * n * np.abs(ref).max())
         np.testing.assert_array_equal(dA.numpy(), A)
         np.testing.assert_array_equal(dA.transpose().numpy(), A.T)
         dA.free()
-    ctx.set_option('gemv_rw', 0)
 
 
 def test_rectangular_and_transposed_products(ctx):
@@ -41,21 +41,20 @@ def test_rectangular_and_transposed_products(ctx):
 @pytest.mark.parametrize('mfma', [0, 1])
 def test_gemm(ctx, mfma):
     rng = np.random.RandomState(2)
-    ctx.set_option('gemm_mfma', mfma)
-    shapes = [(64, 64, 16), (70, 45, 33), (130, 64, 100), (5, 3, 2), (200, 193, 37)]   # last: 128x128 tiles
-    if ctx.backend == 'hip':
-        shapes += [(512, 384, 256), (1000, 1000, 64), (33, 2000, 1500)]
-    for M, N, K in shapes:
-        for tA in (0, 1):
-            for tB in (0, 1):
-                a = rng.normal(size=(K, M) if tA else (M, K))
-                b = rng.normal(size=(N, K) if tB else (K, N))
-                c0 = rng.normal(size=(M, N))
-                dC = ctx.upload(c0)
-                ctx.gemm(ctx.upload(a), ctx.upload(b), dC, tA, tB, 0.7, 0.3)
-                ref = 0.7 * (a.T if tA else a) @ (b.T if tB else b) + 0.3 * c0
-                np.testing.assert_allclose(dC.numpy(), ref, atol=1e-13 * K * max(1, np.abs(ref).max()))
-    ctx.set_option('gemm_mfma', 1)
+    with ctx.options(gemm_mfma=mfma):
+        shapes = [(64, 64, 16), (70, 45, 33), (130, 64, 100), (5, 3, 2), (200, 193, 37)]   # last: 128x128 tiles
+        if ctx.backend == 'hip':
+            shapes += [(512, 384, 256), (1000, 1000, 64), (33, 2000, 1500)]
+        for M, N, K in shapes:
+            for tA in (0, 1):
+                for tB in (0, 1):
+                    a = rng.normal(size=(K, M) if tA else (M, K))
+                    b = rng.normal(size=(N, K) if tB else (K, N))
+                    c0 = rng.normal(size=(M, N))
+                    dC = ctx.upload(c0)
+                    ctx.gemm(ctx.upload(a), ctx.upload(b), dC, tA, tB, 0.7, 0.3)
+                    ref = 0.7 * (a.T if tA else a) @ (b.T if tB else b) + 0.3 * c0
+                    np.testing.assert_allclose(dC.numpy(), ref, atol=1e-13 * K * max(1, np.abs(ref).max()))
 
 
 def test_gemm_identity_with_asymmetric_operand(ctx):
@@ -99,11 +98,8 @@ def test_profiling_hooks(ctx):
     ctx.prof_reset()
     ctx.prof_enable(True)
     ctx.symm_mm(dA, rng.normal(size=n))
-    ctx.set_option('eigh_upd_max', 0)            # the blocked chain at this size too (slot 5 counts ITS matvec launches only)
-    try:
+    with ctx.options(eigh_upd_max=0):            # the blocked chain at this size too (slot 5 counts ITS matvec launches only)
         ctx.eigh(dA)
-    finally:
-        ctx.set_option('eigh_upd_max', 1024)
     ctx.prof_enable(False)
     small, trd = ctx.prof_get(4), ctx.prof_get(5)
     assert small['launches'] >= 1 and small['bytes'] >= 8.0 * n * n and small['ms'] >= 0.0
@@ -137,15 +133,13 @@ def test_block_panel_product(ctx):
         dA = ctx.upload(A)
         ref = A @ X
         tol = 1e-13 * cols * max(1.0, np.abs(ref).max())
-        ctx.set_option('panel_mfma', 1)
-        Y1 = ctx.symm_mm(dA, X)
-        ctx.set_option('panel_mfma', 0)
-        Y0 = ctx.symm_mm(dA, X)
-        ctx.set_option('panel_mfma', 1)
+        with ctx.options(panel_mfma=1):
+            Y1 = ctx.symm_mm(dA, X)
+        with ctx.options(panel_mfma=0):
+            Y0 = ctx.symm_mm(dA, X)
         np.testing.assert_allclose(Y1, ref, atol=tol, rtol=0)
         np.testing.assert_allclose(Y0, ref, atol=tol, rtol=0)
         for rows_per_wg in (32, 48, 64):                          # the launcher picks by size; every variant here
-            ctx.set_option('panel_rows', rows_per_wg)
-            np.testing.assert_allclose(ctx.symm_mm(dA, X), ref, atol=tol, rtol=0)
-        ctx.set_option('panel_rows', 0)
+            with ctx.options(panel_mfma=1, panel_rows=rows_per_wg):
+                np.testing.assert_allclose(ctx.symm_mm(dA, X), ref, atol=tol, rtol=0)
         dA.free()

@@ -121,9 +121,8 @@ def test_general_route_inside_the_call_and_stale_mirrors(ctx):
     ref_rows, _ = _run(_model_search(False, 'tr', 'prfo', 1), 9)
     opt = _model_search(True, 'tr', 'prfo', 1)
     rows = []
-    try:
-        for leg, flag in enumerate((1, 0, 1)):
-            ctx.set_option('lr_dev', flag)
+    for leg, flag in enumerate((1, 0, 1)):
+        with ctx.options(lr_dev=flag):
             got, calls = _run(opt, 3)
             assert calls >= 2
             rows += got
@@ -131,8 +130,6 @@ def test_general_route_inside_the_call_and_stale_mirrors(ctx):
             B = opt.pes.H.B                                    # (rebuilt on demand)
             assert not opt.pes.H._B_stale
             np.testing.assert_array_equal(B, B.T)
-    finally:
-        ctx.set_option('lr_dev', 1)
     for i, (ra, rb) in enumerate(zip(rows, ref_rows)):
         _same_row(ra, rb, i)
 
@@ -165,11 +162,8 @@ def test_batched_trial_steps_on_the_panel_rows(ctx):
     short run is the CPU suite's only pass through that kernel with 15 right-hand sides.)"""
     out = {}
     for batch in (1, 0):
-        ctx.set_option('rs_batch', batch)
-        try:
+        with ctx.options(rs_batch=batch):
             out[batch], _ = _run(_model_search(True, 'ras', 'rfo', 0), 4)
-        finally:
-            ctx.set_option('rs_batch', 0 if ctx.backend == 'emu' else 1)
     for i, (ra, rb) in enumerate(zip(out[1], out[0])):
         np.testing.assert_allclose(ra[0], rb[0], atol=1e-9 * 4 ** i, rtol=0, err_msg=f'step {i}')
         assert ra[2] == pytest.approx(rb[2], rel=1e-9)

@@ -61,11 +61,8 @@ def test_emt_neighbour_lists_that_overflow(ctx):
     S['cutoff'] = big
     e_ref, g_ref = slab.calc.energy_and_gradient(slab.positions)
     par = np.array([S['arr'][k] for k in ('E0', 's0', 'V0', 'eta2', 'kappa', 'lam', 'n0', 'gamma1', 'gamma2')])
-    try:
-        ctx.set_option('emt_hcap', 1)
+    with ctx.options(emt_hcap=1):
         e, g = ctx.emt_eval(slab.positions, par, S['shifts'], S['rc'], S['acut'], big, slab.calc._BETA)
-    finally:
-        ctx.set_option('emt_hcap', 8)
     assert len(slab) * len(S['shifts']) > 2 * 256               # more pairs than one slot per thread holds
     assert abs(e - e_ref) <= 1e-11 * abs(e_ref)
     np.testing.assert_allclose(g, g_ref, atol=1e-11 * np.abs(g_ref).max())

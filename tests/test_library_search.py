@@ -315,16 +315,13 @@ def test_upload_paths_agree(ctx):
     from sella_amd.internal import Constraints
     from sella_amd.search import LibrarySearch
     out = []
-    try:
-        for kmin in (16384, 0, 8):
-            ctx.set_option('h2d_kernel_min', kmin)
+    for kmin in (16384, 0, 8):
+        with ctx.options(h2d_kernel_min=kmin):
             at = _model(ctx, n=126, seed=43)                   # 126: an odd number of doubles in some payloads
             ls = LibrarySearch(at, constraints=Constraints(at), **dict(KW, rs='tr', nsteps_per_diag=3))
             assert not ls.run(0.0, 6)
             out.append((at.positions.copy(), ls.energy, ls.delta))
             ls.close()
-    finally:
-        ctx.set_option('h2d_kernel_min', 16384)
     for o in out[1:]:
         np.testing.assert_array_equal(o[0], out[0][0])
         assert o[1] == out[0][1] and o[2] == out[0][2]

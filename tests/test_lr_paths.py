@@ -11,6 +11,8 @@ and ONE update is driven through the route under test.  The reference is the ora
 that B.  Compared: the spectrum, the matrix rebuilt from (W, mu) (W itself is not unique for clustered mu), W W^T = I,
 the order of mu, the rank bound of include/sella_hip.h, and for the one-call step the trust radius, ratio and proposed
 step against the oracle's restricted step on the updated matrix."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -36,16 +38,9 @@ def structured_everywhere():
 
 @pytest.fixture
 def options(ctx):
-    """ctx.set_option for one test; the defaults come back afterwards."""
-    defaults = dict(lr_chain=1, gemm_mfma=1, gemm_tile128=1, lr_overlap=0, lr_dev=1)
-    touched = []
-
-    def set_option(key, value):
-        touched.append(key)
-        ctx.set_option(key, value)
-    yield set_option
-    for key in touched:
-        ctx.set_option(key, defaults[key])
+    """`options(key, value)` sets an option for the rest of one test; what the context had comes back afterwards."""
+    with contextlib.ExitStack() as stack:
+        yield lambda key, value: stack.enter_context(ctx.options(**{key: value}))
 
 
 # ---- the starting state -------------------------------------------------------------------------------------------

@@ -178,11 +178,10 @@ def test_batched_bisection_matches_sequential(ctx):
         A, P, gvec = hessian_like(n, seed=7 + n, nneg=max(order, 1))
         out = {}
         for flag in (0, 1):
-            ctx.set_option('rs_batch', flag)
-            rs = get_restricted_step('ras')(FakePES(ApproximateHessian, P, gvec, ncons, 1), order, 0.03, method)
-            s, smag = rs.get_s()
+            with ctx.options(rs_batch=flag):
+                rs = get_restricted_step('ras')(FakePES(ApproximateHessian, P, gvec, ncons, 1), order, 0.03, method)
+                s, smag = rs.get_s()
             out[flag] = (s, smag, np.array(rs.alphas))
-        ctx.set_option('rs_batch', 0 if ctx.backend == 'emu' else 1)          # conftest.make_context's setting
         (s0, m0, a0), (s1, m1, a1) = out[0], out[1]
         assert len(a0) > 20                                      # the schedule did reach its bisection phase
         assert abs(len(a0) - len(a1)) <= 1
@@ -213,11 +212,10 @@ def test_batched_bisection_all_measures(ctx):
     for kw in cases:
         out = {}
         for flag in (0, 1):
-            ctx.set_option('rs_batch', flag)
-            st = DeviceStepper(ctx, 'prfo', V, Vt, lam, g, 1)
-            out[flag] = st.restricted_step(delta=0.02, alpha0=1.0, alphamin=0.0, alphamax=1.0, slope=1.0,
-                                           newton_safe=False, tol=1e-15, **kw)
-        ctx.set_option('rs_batch', 0 if ctx.backend == 'emu' else 1)
+            with ctx.options(rs_batch=flag):
+                st = DeviceStepper(ctx, 'prfo', V, Vt, lam, g, 1)
+                out[flag] = st.restricted_step(delta=0.02, alpha0=1.0, alphamin=0.0, alphamax=1.0, slope=1.0,
+                                               newton_safe=False, tol=1e-15, **kw)
         (s0, v0, a0), (s1, v1, a1) = out[0], out[1]
         assert len(a0) > 20 and abs(len(a0) - len(a1)) <= 1, kw['cons']
         k = min(len(a0), len(a1)) - 2

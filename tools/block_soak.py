@@ -43,8 +43,8 @@ for r in range(runs):
         kw.update(Pvecs=Q, PvecsT=Qt, pevals=wq)
     tol = float(rng.choice([1e-7, 1e-9]))
     early = int(rng.randint(2))
-    ctx.set_option('bd_early_matvec', early)
-    out = ctx.davidson_block(dA, n, nev, block=block, tol=tol, maxiter=1500, **kw)
+    with ctx.options(bd_early_matvec=early):
+        out = ctx.davidson_block(dA, n, nev, block=block, tol=tol, maxiter=1500, **kw)
     err = np.abs(out['lams'] - w[:nev]).max()
     ok = out['nconv'] == nev and err < 1e-6
     its.append(out['niter'])
@@ -53,5 +53,4 @@ for r in range(runs):
     if not ok:
         bad.append((r, n, nev, block, kind, tol, early, out['niter'], out['nconv'], err))
         print('FAILED', bad[-1], flush=True)
-ctx.set_option('bd_early_matvec', 1)
 print('%d runs, %d failed, iterations median %d max %d, %.1f s' % (runs, len(bad), int(np.median(its)), max(its), time.perf_counter() - t0))

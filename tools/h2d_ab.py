@@ -16,14 +16,13 @@ if __name__ == '__main__':
     ctx = _dev.get_context()
     for name, make in (('model PES 3N=3072', lambda: model(ctx, 3072)), ('model PES 3N=768', lambda: model(ctx, 768)), ('EMT slab 1024 atoms', slab)):
         for kmin in (16384, 0, 16384, 0):
-            ctx.set_option('h2d_kernel_min', kmin)
-            opt = make()
-            opt.run(fmax=0.0, steps=3)
-            ctx.sync()
-            t = time.perf_counter()
-            opt.run(fmax=0.0, steps=steps)
-            ctx.sync()
-            dt = time.perf_counter() - t
-            print('%-22s h2d_kernel_min %5d: %.3f ms per step, x[0..2] %s' % (name, kmin, 1e3 * dt / steps,
-                  np.array2string(opt.atoms.positions.ravel()[:3], precision=12)), flush=True)
-    ctx.set_option('h2d_kernel_min', 16384)
+            with ctx.options(h2d_kernel_min=kmin):
+                opt = make()
+                opt.run(fmax=0.0, steps=3)
+                ctx.sync()
+                t = time.perf_counter()
+                opt.run(fmax=0.0, steps=steps)
+                ctx.sync()
+                dt = time.perf_counter() - t
+                print('%-22s h2d_kernel_min %5d: %.3f ms per step, x[0..2] %s' % (name, kmin, 1e3 * dt / steps,
+                      np.array2string(opt.atoms.positions.ravel()[:3], precision=12)), flush=True)

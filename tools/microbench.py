@@ -44,12 +44,11 @@ for n in sizes:
     for k in (1, 2, 4, 8):
         X = rng.normal(size=(n, k))
         for rw in (1, 2, 4):
-            ctx.set_option('gemv_rw', rw)
-            p = prof_kind(lambda: ctx.symm_mm(dA, X), 0)
+            with ctx.options(gemv_rw=rw):
+                p = prof_kind(lambda: ctx.symm_mm(dA, X), 0)
             us = 1e3 * p['ms'] / p['launches']
             print(json.dumps(dict(op='gemv_rows', n=n, nrhs=k, rw=rw, us=round(us, 2),
                                   GBs=round(8.0 * n * n / us / 1e3, 1))), flush=True)
-    ctx.set_option('gemv_rw', 0)
     X = rng.normal(size=(n, 2))
     t = timeit(lambda: ctx.tmatmul(dA, X), reps=10)
     print(json.dumps(dict(op='gemv_cols(host-inclusive)', n=n, nrhs=2, us=round(1e6 * t, 1))), flush=True)
@@ -60,13 +59,12 @@ for n in [s for s in sizes if s <= 4096]:
     b = ctx.upload(rng.normal(size=(n, n)))
     c = ctx.zeros(n, n)
     for mf in (1, 0):
-        ctx.set_option('gemm_mfma', mf)
-        for tA, tB in ((0, 0), (0, 1), (1, 0)):
-            p = prof_kind(lambda: ctx.gemm(a, b, c, tA, tB), 1, reps=5)
-            us = 1e3 * p['ms'] / p['launches']
-            print(json.dumps(dict(op='gemm', n=n, mfma=mf, tA=tA, tB=tB, us=round(us, 1),
-                                  TFLOPs=round(2.0 * n ** 3 / us / 1e6, 2))), flush=True)
-    ctx.set_option('gemm_mfma', 1)
+        with ctx.options(gemm_mfma=mf):
+            for tA, tB in ((0, 0), (0, 1), (1, 0)):
+                p = prof_kind(lambda: ctx.gemm(a, b, c, tA, tB), 1, reps=5)
+                us = 1e3 * p['ms'] / p['launches']
+                print(json.dumps(dict(op='gemm', n=n, mfma=mf, tA=tA, tB=tB, us=round(us, 1),
+                                      TFLOPs=round(2.0 * n ** 3 / us / 1e6, 2))), flush=True)
     # skinny shapes of the eigensolver: (n x n)(n x 32) and rank-32 update
     y = ctx.upload(rng.normal(size=(32, n)))
     m = ctx.zeros(n, 32)
@@ -93,10 +91,9 @@ for n in [s for s in sizes if s <= 4096]:
         V.free()
         Vt.free()
     for leaf in (16, 32, 64):
-        ctx.set_option('eigh_leaf', leaf)
-        t = timeit(eig, reps=3, warm=1)
+        with ctx.options(eigh_leaf=leaf):
+            t = timeit(eig, reps=3, warm=1)
         print(json.dumps(dict(op='eigh', n=n, leaf=leaf, ms=round(1e3 * t, 2))), flush=True)
-    ctx.set_option('eigh_leaf', 32)
     ctx.prof_reset()
     ctx.prof_enable(True)
     eig()
