@@ -469,6 +469,17 @@ int sella_emt_eval(sella_ctx* ctx, int n, const double* pos, const double* par, 
 int sella_emt_eval_stress(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
                           const double* shifts, double rc, double acut, double cutoff, double beta,
                           double* energy, double* grad, double* virial6);
+/* The analytic Hessian d2E/dx2 of the same potential (csrc/emt_hessian.hip), arguments and limits as for sella_emt_eval.
+ *   hessian: out (3n x 3n, allocated by the caller) is overwritten and stays on the device; exactly symmetric, and the
+ *     same bit for bit whether or not the neighbour lists of the density pass overflowed (emt_hcap).  Besides `out` it
+ *     needs two n x 3n device matrices for the length of the call (SELLA_E_NOMEM if they cannot be had).
+ *   hvp: HV[q] = H V[q] for k vectors, V and HV (k x 3n) host arrays with one vector per row; no 3n x 3n storage.
+ * A wrong shape of `out`, k <= 0 or a null pointer: SELLA_E_INVALID.                                                */
+int sella_emt_hessian(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
+                      const double* shifts, double rc, double acut, double cutoff, double beta, sella_mat out);
+int sella_emt_hvp(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
+                  const double* shifts, double rc, double acut, double cutoff, double beta,
+                  const double* V, int k, double* HV);
 
 /* ---- calculators that live in the library, and the finite-difference Hessian on top of one ----------------- */
 /* sella/peswrapper.py:413-418 evaluates energy and forces through `atoms.calc`; for a calculator implemented HERE that
@@ -480,6 +491,12 @@ int sella_calc_model_create(sella_ctx* ctx, sella_mat A, const double* U, int nu
 int sella_calc_emt_create(sella_ctx* ctx, int natoms, const double* par, int nshift, const double* shifts, double rc,
                           double acut, double cutoff, double beta, sella_calc** calc);
 int sella_calc_eval(sella_calc* calc, const double* x, double* energy, double* grad);
+/* Second derivatives at x: the Hessian into out (n x n, allocated by the caller, stays on the device), and its products
+ * HV[q] = H V[q] with k host vectors (V, HV: k x n, one vector per row).  emt: sella_emt_hessian / sella_emt_hvp on the
+ * calculator's resident constants, bit for bit; model: A + 2 c sum_j (u_j . x) u_j u_j^T.  Neither counts as a force
+ * call (sella_calc_ncalls is unchanged).  Wrong shapes: SELLA_E_INVALID.                                              */
+int sella_calc_hessian(sella_calc* calc, const double* x, sella_mat out);
+int sella_calc_hvp(sella_calc* calc, const double* x, const double* V, int k, double* HV);
 long sella_calc_ncalls(sella_calc* calc);
 int sella_calc_dim(sella_calc* calc);
 int sella_calc_destroy(sella_calc* calc);

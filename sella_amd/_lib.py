@@ -116,6 +116,8 @@ SIGNATURES = {
     'sella_calc_emt_create': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_double, c_double,
                                       POINTER(c_void_p)]),
     'sella_calc_eval': (c_int, [c_void_p, c_void_p, POINTER(c_double), c_void_p]),
+    'sella_calc_hessian': (c_int, [c_void_p, c_void_p, c_int]),
+    'sella_calc_hvp': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'sella_calc_ncalls': (c_long, [c_void_p]),
     'sella_calc_dim': (c_int, [c_void_p]),
     'sella_calc_destroy': (c_int, [c_void_p]),
@@ -175,6 +177,10 @@ SIGNATURES = {
                                c_double, c_double_p, c_void_p]),
     'sella_emt_eval_stress': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double,
                                       c_double, c_double, c_double_p, c_void_p, c_void_p]),
+    'sella_emt_hessian': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
+                                  c_double, c_int]),
+    'sella_emt_hvp': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
+                              c_double, c_void_p, c_int, c_void_p]),
     'sella_prof_enable': (c_int, [c_void_p, c_int]),
     'sella_prof_reset': (c_int, [c_void_p]),
     'sella_prof_get': (c_int, [c_void_p, c_int, POINTER(c_long), c_double_p, c_double_p, c_double_p]),

@@ -227,16 +227,33 @@ def supports_stress(calc):
     return props is None or 'stress' in props
 
 
+def supports_hessian(calc):
+    """Whether `calc` can produce its own second derivatives (`get_hessian`, `get_device_hessian`,
+    `hessian_vector_product`): a calculator of this module that implements `device_hessian`, or a foreign calculator
+    with a `get_hessian` method."""
+    if calc is None:
+        return False
+    if isinstance(calc, Calculator):
+        return calc.has_hessian
+    return callable(getattr(calc, 'get_hessian', None))
+
+
 class Calculator:
     """energy_and_gradient(positions (N,3)) -> (E, dE/dx (N,3)); results cached per geometry (positions and cell).
     A calculator that also has the virial implements energy_gradient_virial(positions) -> (E, dE/dx, W (6,)), W the
-    derivative of E under a homogeneous strain in Voigt order; get_stress() is then W / V from the same evaluation."""
+    derivative of E under a homogeneous strain in Voigt order; get_stress() is then W / V from the same evaluation.
+    A calculator that has its second derivatives implements device_hessian(positions) -> (3N x 3N) `DeviceMatrix` and
+    hessian_products(positions, V (k, 3N)) -> H V[q] (k, 3N); get_hessian(), get_device_hessian() and
+    hessian_vector_product() are then available (and fit `Sella(..., hessian_function=)`).  They are not force calls:
+    `ncalls` does not move, `nhessians` counts the evaluations."""
 
     def __init__(self):
         self._key = None
         self._res = None
         self._virial = None
         self._ncalls = 0
+        self._hess = None                  # (cache key, DeviceMatrix, ndarray or None) of the last Hessian
+        self.nhessians = 0                 # Hessians and batches of Hessian-vector products evaluated
 
     def _library_calls(self):
         dc = getattr(self, '_devcalc', None)
@@ -259,6 +276,57 @@ class Calculator:
 
     def energy_gradient_virial(self, pos):
         raise NotImplementedError(f'{type(self).__name__} has no stress tensor')
+
+    def device_hessian(self, pos):
+        raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian')
+
+    def hessian_products(self, pos, V):
+        raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian')
+
+    has_hessian = property(lambda self: type(self).device_hessian is not Calculator.device_hessian)
+
+    def _prepare(self, atoms):
+        """Whatever depends on the species and the cell of `atoms` rather than on the positions (nothing here)."""
+
+    def _drop_hessian(self):
+        if self._hess is not None:
+            self._hess[1].free()
+        self._hess = None
+
+    def _cached_hessian(self, atoms):
+        if not self.has_hessian:
+            raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian')
+        self._prepare(atoms)
+        key = cache_key(atoms)
+        if self._hess is None or self._hess[0] != key or self._hess[1].ctx._h is None:     # (or its context is gone)
+            self._drop_hessian()
+            self._hess = [key, self.device_hessian(atoms.positions), None]
+            self.nhessians += 1
+        return self._hess
+
+    def get_device_hessian(self, atoms):
+        """The Cartesian Hessian d2E/dx2 (3N x 3N) of the geometry of `atoms` as a `DeviceMatrix` of the caller's own (a
+        device copy of the cached one: `ApproximateHessian.set_B` keeps what it is given)."""
+        return self._cached_hessian(atoms)[1].copy()
+
+    def get_hessian(self, atoms):
+        """The same as an array (one download per geometry)."""
+        hit = self._cached_hessian(atoms)
+        if hit[2] is None:
+            hit[2] = hit[1].numpy()
+        return hit[2].copy()
+
+    def hessian_vector_product(self, atoms, V):
+        """H v for one vector (3N,) or the rows of V (k, 3N), without forming H; the shape of V."""
+        if not self.has_hessian:
+            raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian')
+        self._prepare(atoms)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        n = 3 * len(atoms)
+        if V.shape != (n,) and (V.ndim != 2 or V.shape[1] != n or V.shape[0] == 0):
+            raise ValueError(f'expected vectors of length {n} as an array of shape ({n},) or (k, {n}), got {V.shape}')
+        self.nhessians += 1
+        return np.asarray(self.hessian_products(atoms.positions, V.reshape(-1, n))).reshape(V.shape)
 
     def _get(self, atoms, stress=False):
         """(E, dE/dx) of the geometry of `atoms`; with `stress`, the virial is cached alongside them from the same
@@ -311,6 +379,15 @@ class QuadraticCubicModel(Calculator):
             from .device import DeviceCalculator
             self._devcalc = DeviceCalculator.model(self.device_matrix.ctx, self.device_matrix, self.U, self.c)
         return self._devcalc
+
+    # second derivatives A + 2 c sum_j (u_j . x) u_j u_j^T: through the library's copy of the calculator only
+    has_hessian = property(lambda self: self.device_matrix is not None)
+
+    def device_hessian(self, pos):
+        return self.device_calculator().hessian(np.asarray(pos).ravel())
+
+    def hessian_products(self, pos, V):
+        return self.device_calculator().hvp(np.asarray(pos).ravel(), V)
 
     def energy_and_gradient(self, pos):
         x = pos.ravel()
@@ -405,7 +482,9 @@ class EMT(Calculator):
     ASE; checked against the NumPy restatement in oracle/ and finite differences of its own energy.  Periodic
     directions are handled by an explicit sum over the periodic images: ceil(cutoff / height) of them on either side
     along each periodic direction (one while the cell is at least a cutoff, ~5.3 A for Cu, wide), 127 images at most.
-    get_stress() takes energy, forces and the virial from one device evaluation (`sella_emt_eval_stress`)."""
+    get_stress() takes energy, forces and the virial from one device evaluation (`sella_emt_eval_stress`);
+    get_hessian() / get_device_hessian() / hessian_vector_product() are the analytic second derivatives
+    (`sella_emt_hessian`, `sella_emt_hvp`)."""
     #              E0     s0    V0     eta2   kappa  lambda n0        (eV, bohr, eV, 1/bohr, 1/bohr, 1/bohr, 1/bohr^3)
     _PAR = dict(Al=(-3.28, 3.00, 1.493, 1.240, 2.000, 1.169, 0.00700), Cu=(-3.51, 2.67, 2.476, 1.652, 2.740, 1.906, 0.00910),
                 Ag=(-2.96, 3.01, 2.132, 1.652, 2.790, 1.892, 0.00547), Au=(-3.80, 3.00, 2.321, 1.674, 2.873, 2.182, 0.00703),
@@ -418,11 +497,15 @@ class EMT(Calculator):
         super().__init__()
         self._setup = None
 
-    def _get(self, atoms, stress=False):
+    def _prepare(self, atoms):
         key = (tuple(atoms.symbols), np.asarray(atoms.cell, dtype=float).tobytes(), tuple(atoms.pbc))
         if self._setup is None or self._setup[0] != key:
             self._setup = (key, self._initialize(atoms))
             self._key = None                       # results cached for the old cell / species are stale
+            self._drop_hessian()
+
+    def _get(self, atoms, stress=False):
+        self._prepare(atoms)
         return super()._get(atoms, stress)
 
     def _initialize(self, atoms):
@@ -486,6 +569,19 @@ class EMT(Calculator):
         from .device import get_context
         S = self._setup[1]
         return get_context().emt_eval_stress(pos, S['par'], S['shifts'], S['rc'], S['acut'], S['cutoff'], self._BETA)
+
+    def _emt_args(self, pos):
+        S = self._setup[1]
+        return pos, S['par'], S['shifts'], S['rc'], S['acut'], S['cutoff'], self._BETA
+
+    def device_hessian(self, pos):
+        """The analytic Hessian (csrc/emt_hessian.hip: pair blocks per atom, the embedding term as one rank-N product)."""
+        from .device import get_context
+        return get_context().emt_hessian(*self._emt_args(pos))
+
+    def hessian_products(self, pos, V):
+        from .device import get_context
+        return get_context().emt_hvp(*self._emt_args(pos), V)
 
     library_form = True
 

@@ -164,6 +164,84 @@ extern "C" int sella_calc_eval(sella_calc* k, const double* x, double* f, double
     return SELLA_OK;
 }
 
+// Second derivatives at x: `out` (n x n, the caller's) stays on the device.  EMT: emt_hessian.hip on the resident
+// constants; model: A + 2 c sum_j (u_j . x) u_j u_j^T, the rows u_j scaled on the host and one rank-nu product.
+// Not force calls: ncalls is unchanged.
+extern "C" int sella_calc_hessian(sella_calc* k, const double* x, sella_mat out) {
+    if (!k || !x) {
+        set_error("calc_hessian: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    sella_ctx* c = k->c;
+    if (k->kind == 1)
+        return emt_hessian_resident(c, k->natoms, x, k->par.data(), k->nshift, k->shifts.data(), k->dconst, k->rc, k->acut,
+                                    k->cutoff, k->beta, out);
+    const int n = k->n, nu = k->nu, ld = round_up(n, 8);
+    Mat *A = mat_get(c, k->A), *H = mat_get(c, out);
+    if (!A) {
+        set_error("calc_hessian: the model calculator's matrix A is gone");
+        return SELLA_E_INVALID;
+    }
+    if (!H || H->rows != n || H->cols != n) {
+        set_error("calc_hessian: out must be %d x %d", n, n);
+        return SELLA_E_INVALID;
+    }
+    SCHK(launch_axpby2d(c, n, n, 1.0, A->d, A->ld, 0.0, nullptr, 0, H->d, H->ld));
+    if (nu > 0) {
+        std::vector<double>& S = c->hbuf_b;                            // rows 2 c (u_j . x) u_j, padded like the resident rows
+        S.assign((size_t)nu * ld, 0.0);
+        for (int j = 0; j < nu; ++j) {
+            const double* u = k->U.data() + (size_t)j * n;
+            double p = 0.0;
+            for (int i = 0; i < n; ++i) p += u[i] * x[i];
+            for (int i = 0; i < n; ++i) S[(size_t)j * ld + i] = 2.0 * k->cc * p * u[i];
+        }
+        double* dS;
+        SCHK(scratch_get(c, SCR_MISC0, (size_t)nu * ld * sizeof(double), &dS));
+        SCHK(h2d_async(c, dS, S.data(), (size_t)nu * ld * sizeof(double)));
+        SCHK(launch_gemm(c, 1, 0, n, n, nu, 1.0, dS, ld, k->dconst, ld, 1.0, H->d, H->ld));
+    }
+    return stream_wait(c);
+}
+
+// H V^T for k vectors (V, HV: (k, n) host arrays, one vector per row), without the matrix for the EMT kind
+extern "C" int sella_calc_hvp(sella_calc* k, const double* x, const double* V, int nv, double* HV) {
+    if (!k || !x || !V || nv <= 0 || !HV) {
+        set_error("calc_hvp: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    sella_ctx* c = k->c;
+    if (k->kind == 1)
+        return emt_hvp_resident(c, k->natoms, x, k->par.data(), k->nshift, k->shifts.data(), k->dconst, k->rc, k->acut,
+                                k->cutoff, k->beta, V, nv, HV);
+    const int n = k->n, nu = k->nu, ld = round_up(n, 8);
+    Mat* A = mat_get(c, k->A);
+    if (!A) {
+        set_error("calc_hvp: the model calculator's matrix A is gone");
+        return SELLA_E_INVALID;
+    }
+    double* buf;                                                       // V | A V (rows of ld)
+    SCHK(scratch_get(c, SCR_MISC0, (size_t)2 * nv * ld * sizeof(double), &buf));
+    double *dV = buf, *dAV = buf + (size_t)nv * ld;
+    HIPCHK(s_memset0(c, dV, (size_t)nv * ld * sizeof(double)));
+    for (int q = 0; q < nv; ++q) SCHK(h2d_async(c, dV + (size_t)q * ld, V + (size_t)q * n, (size_t)n * sizeof(double)));
+    SCHK(launch_gemm(c, 0, 1, nv, n, n, 1.0, dV, ld, A->d, A->ld, 0.0, dAV, ld));     // row q: (A v_q)^T
+    SCHK(d2h_async_2d(c, HV, dAV, (size_t)ld * sizeof(double), (size_t)n * sizeof(double), (size_t)nv));
+    SCHK(stream_wait(c));
+    for (int j = 0; j < nu; ++j) {                                     // + 2 c (u_j . x) (u_j . v_q) u_j
+        const double* u = k->U.data() + (size_t)j * n;
+        double p = 0.0;
+        for (int i = 0; i < n; ++i) p += u[i] * x[i];
+        for (int q = 0; q < nv; ++q) {
+            double t = 0.0;
+            for (int i = 0; i < n; ++i) t += u[i] * V[(size_t)q * n + i];
+            const double f = 2.0 * k->cc * p * t;
+            for (int i = 0; i < n; ++i) HV[(size_t)q * n + i] += f * u[i];
+        }
+    }
+    return SELLA_OK;
+}
+
 extern "C" long sella_calc_ncalls(sella_calc* k) { return k ? k->ncalls : 0; }
 extern "C" int sella_calc_dim(sella_calc* k) { return k ? k->n : 0; }
 extern "C" int sella_calc_destroy(sella_calc* k) {

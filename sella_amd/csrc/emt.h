@@ -1,0 +1,49 @@
+// emt.h — what the effective-medium-theory kernels share (emt.hip: energy, forces, virial; emt_hessian.hip: second
+// derivatives): the argument block, the in-block reduction, and the format of the per-thread neighbour lists the density
+// pass hands on.
+#pragma once
+#include "internal.h"
+
+namespace sella {
+
+struct EmtPar {             // per-atom parameters, already converted to eV / Angstrom
+    const double *E0, *s0, *V0, *eta2, *kappa, *lam, *n0, *gamma1, *gamma2;
+};
+
+struct EmtArgs {
+    int n, nshift;
+    int hcap;               // slots of a thread's neighbour list in use (<= EMT_HCAP; option emt_hcap, tests lower it)
+    const double* pos;      // n x 3
+    const double* shifts;   // nshift x 3 lattice translations (including 0)
+    EmtPar p;
+    double rc, acut, cutoff, beta;
+    double* sigma1; double* epair; double* dEdsig; double* eatom; double* grad;
+    int* nbr;               // n x 256 x (1 + EMT_HCAP): neighbour lists of the density kernel's threads, for the force kernel
+};
+
+namespace {
+
+__device__ __forceinline__ double block_sum(double v, double* red) {
+    v = wave_sum64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+constexpr int EMT_HCAP = 8;                // slots of a thread's neighbour list
+
+// a noted pair: atom index in the low 24 bits, image above (no division when it is taken up again)
+__device__ __forceinline__ int emt_pack(int j, int s) { return (s << 24) | j; }
+
+}  // namespace
+
+// emt.hip: positions uploaded (parameter table and shifts too unless `dconst` holds them, see emt_eval_resident), the
+// argument block filled in and the density pass queued: sigma1, dEdsig and the neighbour lists of this geometry are then
+// on the device, in scratch slot SCR_MISC0, with `extra_words` more doubles behind them at *extra for the caller's own
+// intermediates.  Nothing is waited for.
+int emt_density_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                      const double* dconst, double rc, double acut, double cutoff, double beta, size_t extra_words,
+                      EmtArgs* args, double** extra);
+
+}  // namespace sella

@@ -10,33 +10,10 @@
 //   pass 1: sigma1_i = sum_j dsigma(i <- j), pair energy of atom i
 //           cohesive function, dE/dsigma1_i                           (own density only: at the end of pass 1)
 //   pass 2: F_i by gathering both ordered pairs (i <- j) and (j <- i) of every neighbour
-#include "internal.h"
+#include "emt.h"
 
 namespace sella {
 namespace {
-
-struct EmtPar {             // per-atom parameters, already converted to eV / Angstrom
-    const double *E0, *s0, *V0, *eta2, *kappa, *lam, *n0, *gamma1, *gamma2;
-};
-
-struct EmtArgs {
-    int n, nshift;
-    int hcap;               // slots of a thread's neighbour list in use (<= EMT_HCAP; option emt_hcap, tests lower it)
-    const double* pos;      // n x 3
-    const double* shifts;   // nshift x 3 lattice translations (including 0)
-    EmtPar p;
-    double rc, acut, cutoff, beta;
-    double* sigma1; double* epair; double* dEdsig; double* eatom; double* grad;
-    int* nbr;               // n x 256 x (1 + EMT_HCAP): neighbour lists of the density kernel's threads, for the force kernel
-};
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-    v = wave_sum64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // The sweep over all (neighbour, image) pairs is split in two per thread: first the distance test alone over the thread's
 // pairs (t = tid, tid + 256, ...: no division, squared distance against a slightly widened cutoff), the few pairs inside
@@ -44,11 +21,7 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 // expensive branch inside the sweep every second wavefront iteration took it for some lane; deferred, a wavefront
 // pays for the largest number of neighbours any of its lanes found (2-3).  The terms are added per thread in the same
 // order as before — sums are bit-identical to the one-loop form.
-constexpr int EMT_HCAP = 8;
 constexpr int EMT_LDS_ATOMS = 1024;       // up to this many atoms the positions are staged in LDS (structure of arrays)
-
-// a noted pair: atom index in the low 24 bits, image above (no division when it is taken up again)
-__device__ __forceinline__ int emt_pack(int j, int s) { return (s << 24) | j; }
 
 struct EmtStage {
     double x[EMT_LDS_ATOMS], y[EMT_LDS_ATOMS], z[EMT_LDS_ATOMS];
@@ -276,19 +249,16 @@ int sella::emt_eval_resident(sella_ctx* c, int n, const double* pos, const doubl
     return SELLA_OK;
 }
 
-// the same up to the kernels: positions uploaded, two launches queued, nothing waited for.  *eatom (n per-atom
-// energies, summed by the caller in index order) and *grad (3 n, directly behind; with `virial`, the n x 6 per-atom
-// virials directly behind that) stay valid until scratch slot SCR_MISC0 is used again.
-int sella::emt_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
-                     const double* dconst, double rc, double acut, double cutoff, double beta, double** eatom, double** grad,
-                     bool virial) {
+int sella::emt_density_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                             const double* dconst, double rc, double acut, double cutoff, double beta, size_t extra_words,
+                             EmtArgs* args, double** extra) {
     if (n >= (1 << 24) || nshift > 127) { set_error("emt: at most 2^24 atoms and 127 periodic images"); return SELLA_E_INVALID; }
-    const size_t nvir = virial ? (size_t)6 * n : 0;
     const size_t nbr_words = ((size_t)n * 256 * (EMT_HCAP + 1) + 1) / 2;
-    const size_t words = (size_t)3 * n + (size_t)9 * n + (size_t)3 * nshift + (size_t)4 * n + (size_t)3 * n + nvir + 64
+    // (the six virial words per atom are always part of the layout: the lists sit at the same place for every caller)
+    const size_t words = (size_t)3 * n + (size_t)9 * n + (size_t)3 * nshift + (size_t)4 * n + (size_t)3 * n + (size_t)6 * n + 64
                          + nbr_words;
     double* buf;
-    SCHK(scratch_get(c, SCR_MISC0, words * sizeof(double), &buf));
+    SCHK(scratch_get(c, SCR_MISC0, (words + extra_words) * sizeof(double), &buf));
     double* dpos = buf;
     double* dpar = dpos + 3 * (size_t)n;
     double* dsh = dpar + 9 * (size_t)n;
@@ -313,15 +283,29 @@ int sella::emt_queue(sella_ctx* c, int n, const double* pos, const double* par, 
     a.p.gamma1 = dpar + 7 * (size_t)n; a.p.gamma2 = dpar + 8 * (size_t)n;
     a.rc = rc; a.acut = acut; a.cutoff = cutoff; a.beta = beta;
     a.sigma1 = dsig; a.epair = dep; a.dEdsig = dde; a.eatom = dea; a.grad = dgr;
-    a.nbr = reinterpret_cast<int*>(dgr + 3 * (size_t)n + nvir + 32);
+    a.nbr = reinterpret_cast<int*>(dgr + 3 * (size_t)n + 6 * (size_t)n + 32);
     SELLA_LAUNCHB(c, emt_density_kernel, emt_density_vb, 256, dim3(n), dim3(256), 0, a);
+    HIPCHK(hipGetLastError());
+    *args = a;
+    if (extra) *extra = buf + words;
+    return SELLA_OK;
+}
+
+// the same up to the kernels: positions uploaded, two launches queued, nothing waited for.  *eatom (n per-atom
+// energies, summed by the caller in index order) and *grad (3 n, directly behind; with `virial`, the n x 6 per-atom
+// virials directly behind that) stay valid until scratch slot SCR_MISC0 is used again.
+int sella::emt_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                     const double* dconst, double rc, double acut, double cutoff, double beta, double** eatom, double** grad,
+                     bool virial) {
+    EmtArgs a;
+    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, 0, &a, nullptr));
     if (virial)
         SELLA_LAUNCHB(c, emt_force_virial_kernel, emt_force_virial_vb, 256, dim3(n), dim3(256), 0, a);
     else
         SELLA_LAUNCHB(c, emt_force_kernel, emt_force_vb, 256, dim3(n), dim3(256), 0, a);
     HIPCHK(hipGetLastError());
-    *eatom = dea;
-    *grad = dgr;
+    *eatom = a.eatom;
+    *grad = a.grad;
     return SELLA_OK;
 }
 

@@ -381,6 +381,12 @@ int emt_eval_resident(sella_ctx* c, int n, const double* pos, const double* par,
                       double* virial6 = nullptr);
 int emt_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts, const double* dconst,
               double rc, double acut, double cutoff, double beta, double** eatom, double** grad, bool virial = false);
+// emt_hessian.hip: the analytic Hessian of the same potential into `out` (3n x 3n, stays on the device) and its products
+// with k host vectors (V, HV: (k, 3n)); dconst as above
+int emt_hessian_resident(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                         const double* dconst, double rc, double acut, double cutoff, double beta, sella_mat out);
+int emt_hvp_resident(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                     const double* dconst, double rc, double acut, double cutoff, double beta, const double* V, int k, double* HV);
 // calc.hip: a force call of a library calculator in two halves, so that what consumes the gradient can be queued behind
 // it without a wait in between.  calc_queue: x (host) uploaded, kernels queued; *g_dev = gradient on the device (n),
 // *aux_dev / *naux = what the energy is assembled from.  calc_finish: energy from the read-back aux values, after the wait.

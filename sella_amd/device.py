@@ -625,6 +625,30 @@ class Context:
                                                float(acut), float(cutoff), float(beta), byref(e), ptr(grad), ptr(virial)))
         return e.value, grad, virial
 
+    def emt_hessian(self, pos, par, shifts, rc, acut, cutoff, beta):
+        """The analytic Cartesian Hessian of the EMT potential as a (3n x 3n) `DeviceMatrix` (`sella_emt_hessian`):
+        arguments as for `emt_eval`; exactly symmetric, left on the device."""
+        pos = as_f64(pos)
+        par = as_f64(par)
+        shifts = as_f64(shifts)
+        n = pos.shape[0]
+        out = self.zeros(3 * n, 3 * n)
+        check(_lib.lib().sella_emt_hessian(self._h, n, ptr(pos), ptr(par), shifts.shape[0], ptr(shifts), float(rc),
+                                           float(acut), float(cutoff), float(beta), out.handle))
+        return out
+
+    def emt_hvp(self, pos, par, shifts, rc, acut, cutoff, beta, V):
+        """H V[q] for the rows of V (k, 3n) (or one vector (3n,)) without forming H (`sella_emt_hvp`); same shape as V."""
+        pos = as_f64(pos)
+        par = as_f64(par)
+        shifts = as_f64(shifts)
+        n = pos.shape[0]
+        V, shape = _hvp_vectors(V, 3 * n)
+        HV = np.empty_like(V)
+        check(_lib.lib().sella_emt_hvp(self._h, n, ptr(pos), ptr(par), shifts.shape[0], ptr(shifts), float(rc),
+                                       float(acut), float(cutoff), float(beta), ptr(V), V.shape[0], ptr(HV)))
+        return HV.reshape(shape)
+
     # ---- profiling ---------------------------------------------------------------------------
     def prof_enable(self, on=True):
         check(_lib.lib().sella_prof_enable(self._h, int(bool(on))))
@@ -636,6 +660,17 @@ class Context:
         n, ms, b, f = c_long(0), c_double(0), c_double(0), c_double(0)
         check(_lib.lib().sella_prof_get(self._h, int(kind), byref(n), byref(ms), byref(b), byref(f)))
         return dict(launches=n.value, ms=ms.value, bytes=b.value, flops=f.value)
+
+
+def _hvp_vectors(V, n):
+    """((k, n) contiguous fp64 array, shape to hand the products back in) for one vector (n,) or k vectors (k, n)."""
+    V = as_f64(V)
+    shape = V.shape
+    if V.ndim == 1:
+        V = V.reshape(1, -1)
+    if V.ndim != 2 or V.shape[1] != n or V.shape[0] == 0:
+        raise ValueError(f'expected vectors of length {n} as an array of shape ({n},) or (k, {n}), got {shape}')
+    return np.ascontiguousarray(V), shape
 
 
 class DeviceCalculator:
@@ -667,6 +702,21 @@ class DeviceCalculator:
         g = np.empty(x.size)
         check(_lib.lib().sella_calc_eval(self._h, ptr(x), byref(e), ptr(g)))
         return e.value, g
+
+    def hessian(self, x):
+        """The Hessian at x as an (n x n) `DeviceMatrix` (`sella_calc_hessian`); not a force call."""
+        x = as_f64(x).ravel()
+        out = self.ctx.zeros(x.size, x.size)
+        check(_lib.lib().sella_calc_hessian(self._h, ptr(x), out.handle))
+        return out
+
+    def hvp(self, x, V):
+        """H V[q] for the rows of V (k, n) (or one vector (n,)) (`sella_calc_hvp`); same shape as V."""
+        x = as_f64(x).ravel()
+        V, shape = _hvp_vectors(V, x.size)
+        HV = np.empty_like(V)
+        check(_lib.lib().sella_calc_hvp(self._h, ptr(x), ptr(V), V.shape[0], ptr(HV)))
+        return HV.reshape(shape)
 
     ncalls = property(lambda self: int(_lib.lib().sella_calc_ncalls(self._h)))
 

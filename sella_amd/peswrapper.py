@@ -997,7 +997,7 @@ class InternalPES(PES):
             self._real_factor_cache.put(key, cached)
         return cached
 
-    def _convert_cartesian_hessian_to_internal(self, Hcart):
+    def _convert_cartesian_hessian_to_internal(self, Hcart, consume=False):
         """The internal-coordinate Hessian of the Cartesian Hessian Hcart (3N x 3N, real atoms) as a `DeviceMatrix`
         (nint x nint): with B = B[:, :3N] = U_r S_r V_r^T (singular values above 1e-6), X = V_r S_r^-1 and Q = U_r,
         Hnred = X^T (Hcart - sum_i g_i d2q_i/dx2) X and lambda_bar the geometric mean of |eig(Hnred)|, the result is
@@ -1005,26 +1005,40 @@ class InternalPES(PES):
         taken from the eigenvalues of the symmetric part of Hnred, which for an asymmetric Hcart (finite differences)
         differ from those of the one triangle the reference's eigh reads.  Runs on the device
         (`sella_hessian_cart_to_int`); dummy degrees of freedom enter as zero rows and columns of Hcart and zero rows of
-        X."""
+        X.  Hcart may be a `DeviceMatrix` (a calculator's own): it is not taken to the host and back.  The conversion
+        overwrites its input, so it works on a device copy — unless `consume` hands the matrix over, which is then used
+        as it is and freed."""
+        from .device import DeviceMatrix
         n, nx = 3 * len(self.atoms), self.int.ndof
-        Hcart = np.asarray(Hcart, dtype=np.float64)
+        on_device = isinstance(Hcart, DeviceMatrix)        # (a calculator's own, e.g. EMT.get_device_hessian: not copied
+        if not on_device:                                  # to the host and back)
+            Hcart = np.asarray(Hcart, dtype=np.float64)
         if Hcart.shape != (n, n):
             raise ValueError(f'hessian_function must return the {n} x {n} Cartesian Hessian of the {len(self.atoms)} '
                              f'atoms, got an array of shape {Hcart.shape}')
         fac = self._get_real_factor()
         X, Q = fac.BinvQ, fac.Q
+        ctx = get_context()
+        given = Hcart if on_device and consume else None
+        if on_device and nx != n:                          # dummy atoms: the zero frame around it is put on on the host
+            Hcart, on_device = Hcart.numpy(), False
+        if on_device:
+            hH = Hcart if consume else Hcart.copy()
         if nx != n:
             Hcart = np.pad(Hcart, ((0, nx - n), (0, nx - n)))
             X = np.pad(X, ((0, nx - n), (0, 0)))
         g = self.get_g()
         hess = self.int.sparse_hessians()                  # B and the d2q_i/dx2 of this geometry, on the device
-        ctx = get_context()
-        hH, hX, hQ = ctx.upload(Hcart), ctx.upload(X), ctx.upload(Q)
+        if not on_device:
+            hH = ctx.upload(Hcart)
+        hX, hQ = ctx.upload(X), ctx.upload(Q)
         try:
             out, _ = ctx.hessian_cart_to_int(hess._device(), g, hH, hX, hQ)
         finally:
             for h in (hH, hX, hQ):
                 h.free()
+            if given is not None:
+                given.free()                               # (no-op if it was hH)
         return out
 
     def _convert_internal_hessian_to_cartesian(self, Hint):
@@ -1043,7 +1057,8 @@ class InternalPES(PES):
 
     def calculate_hessian(self):
         assert self.hessian_function is not None
-        self.H.set_B(self._convert_cartesian_hessian_to_internal(self.hessian_function(self.atoms)))
+        # what the hessian_function returns is the PES's from here on, as in `PES.calculate_hessian` (set_B keeps it)
+        self.H.set_B(self._convert_cartesian_hessian_to_internal(self.hessian_function(self.atoms), consume=True))
 
     def kick(self, dx, diag=False, **diag_kwargs):
         # A geodesic that runs into a degenerate internal coordinate (an angle close to 0 or pi) stops there:
