@@ -78,6 +78,10 @@ int sella_mat_transpose(sella_ctx* ctx, sella_mat src, sella_mat* dst);
 int sella_mat_rows(sella_ctx* ctx, sella_mat src, int row0, int nrows, sella_mat* dst);
 /* dst rows [0, nrows) <- src rows [0, nrows) (equal column counts): growing such a buffer                          */
 int sella_mat_copy_into(sella_ctx* ctx, sella_mat src, sella_mat dst, int nrows);
+/* dst[drow + i][dcol + j] <- src[srow + i][scol + j] for a rows x cols block (src and dst different matrices; a block
+ * that leaves either matrix: SELLA_E_INVALID): a principal block of one matrix into a frame of another size           */
+int sella_mat_copy_block(sella_ctx* ctx, sella_mat src, int srow, int scol, int rows, int cols, sella_mat dst, int drow,
+                         int dcol);
 /* A[i][i] += alpha: B = lam0 * I of the first-update rule (sella/linalg.py:274-289) is a zero matrix plus this      */
 int sella_mat_add_diag(sella_ctx* ctx, sella_mat h, double alpha);
 int sella_mat_free(sella_ctx* ctx, sella_mat h);
@@ -480,6 +484,19 @@ int sella_emt_hessian(sella_ctx* ctx, int n, const double* pos, const double* pa
 int sella_emt_hvp(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
                   const double* shifts, double rc, double acut, double cutoff, double beta,
                   const double* V, int k, double* HV);
+/* The analytic Hessian of positions AND cell, in the coordinates [x (3n Cartesian positions); C.ravel() (the nine cell
+ * entries, row-major, lattice vectors in the rows of C)], the positions held fixed while C varies (the convention of
+ * set_cell(scale_atoms=False)).  cell (9): C; shifts must be whole-number combinations n_s C of its rows — the image
+ * indices n_s = S_s C^-1 are worked out here, and the cell enters the energy through them alone, so a lattice vector no
+ * shift uses (a non-periodic direction) gives zero rows and columns.  out ((3n + 9) square, allocated by the caller) is
+ * overwritten and stays on the device: exactly symmetric, the same bit for bit whether or not the neighbour lists
+ * overflowed, and its leading 3n x 3n block is bit for bit sella_emt_hessian's (the same passes, written with the wider
+ * row stride).  Other arguments, limits and temporary storage as for sella_emt_hessian, plus one n x 9 device matrix.
+ * A wrong shape of `out`, a null pointer, a singular cell, or a shift whose image index is not whole to 1e-6:
+ * SELLA_E_INVALID.                                                                                                  */
+int sella_emt_cell_hessian(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
+                           const double* shifts, const double* cell, double rc, double acut, double cutoff, double beta,
+                           sella_mat out);
 
 /* ---- calculators that live in the library, and the finite-difference Hessian on top of one ----------------- */
 /* sella/peswrapper.py:413-418 evaluates energy and forces through `atoms.calc`; for a calculator implemented HERE that

@@ -74,6 +74,7 @@ SIGNATURES = {
     'sella_mat_transpose': (c_int, [c_void_p, c_int, c_int_p]),
     'sella_mat_rows': (c_int, [c_void_p, c_int, c_int, c_int, c_int_p]),
     'sella_mat_copy_into': (c_int, [c_void_p, c_int, c_int, c_int]),
+    'sella_mat_copy_block': (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'sella_mat_add_diag': (c_int, [c_void_p, c_int, c_double]),
     'sella_mat_free': (c_int, [c_void_p, c_int]),
     'sella_mat_axpby': (c_int, [c_void_p, c_double, c_int, c_double, c_int, c_int_p]),
@@ -181,6 +182,8 @@ SIGNATURES = {
                                   c_double, c_int]),
     'sella_emt_hvp': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double, c_double,
                               c_double, c_void_p, c_int, c_void_p]),
+    'sella_emt_cell_hessian': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double,
+                                       c_double, c_double, c_int]),
     'sella_prof_enable': (c_int, [c_void_p, c_int]),
     'sella_prof_reset': (c_int, [c_void_p]),
     'sella_prof_get': (c_int, [c_void_p, c_int, POINTER(c_long), c_double_p, c_double_p, c_double_p]),

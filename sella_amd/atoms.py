@@ -238,6 +238,17 @@ def supports_hessian(calc):
     return callable(getattr(calc, 'get_hessian', None))
 
 
+def supports_cell_hessian(calc):
+    """Whether `calc` can produce the second derivatives of positions and cell together (`get_cell_hessian`,
+    `get_device_cell_hessian`): a calculator of this module that implements `device_cell_hessian`, or a foreign
+    calculator with a `get_cell_hessian` method."""
+    if calc is None:
+        return False
+    if isinstance(calc, Calculator):
+        return calc.has_cell_hessian
+    return callable(getattr(calc, 'get_cell_hessian', None))
+
+
 class Calculator:
     """energy_and_gradient(positions (N,3)) -> (E, dE/dx (N,3)); results cached per geometry (positions and cell).
     A calculator that also has the virial implements energy_gradient_virial(positions) -> (E, dE/dx, W (6,)), W the
@@ -245,7 +256,12 @@ class Calculator:
     A calculator that has its second derivatives implements device_hessian(positions) -> (3N x 3N) `DeviceMatrix` and
     hessian_products(positions, V (k, 3N)) -> H V[q] (k, 3N); get_hessian(), get_device_hessian() and
     hessian_vector_product() are then available (and fit `Sella(..., hessian_function=)`).  They are not force calls:
-    `ncalls` does not move, `nhessians` counts the evaluations."""
+    `ncalls` does not move, `nhessians` counts the evaluations.
+    A calculator that also has the second derivatives with respect to the cell implements
+    device_cell_hessian(positions, cell) -> (3N + 9)-square `DeviceMatrix` in the coordinates [positions; cell.ravel()]
+    (lattice vectors in the rows of the cell, positions fixed while the cell varies); get_cell_hessian() and
+    get_device_cell_hessian() are then available (and fit `Sella(..., optimize_cell=True, hessian_function=)`), cached
+    and counted like the Hessian at fixed cell."""
 
     def __init__(self):
         self._key = None
@@ -253,6 +269,7 @@ class Calculator:
         self._virial = None
         self._ncalls = 0
         self._hess = None                  # (cache key, DeviceMatrix, ndarray or None) of the last Hessian
+        self._cell_hess = None             # the same of the last Hessian of positions and cell
         self.nhessians = 0                 # Hessians and batches of Hessian-vector products evaluated
 
     def _library_calls(self):
@@ -283,15 +300,20 @@ class Calculator:
     def hessian_products(self, pos, V):
         raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian')
 
+    def device_cell_hessian(self, pos, cell):
+        raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian of positions and cell')
+
     has_hessian = property(lambda self: type(self).device_hessian is not Calculator.device_hessian)
+    has_cell_hessian = property(lambda self: type(self).device_cell_hessian is not Calculator.device_cell_hessian)
 
     def _prepare(self, atoms):
         """Whatever depends on the species and the cell of `atoms` rather than on the positions (nothing here)."""
 
     def _drop_hessian(self):
-        if self._hess is not None:
-            self._hess[1].free()
-        self._hess = None
+        for hit in (self._hess, self._cell_hess):
+            if hit is not None:
+                hit[1].free()
+        self._hess = self._cell_hess = None
 
     def _cached_hessian(self, atoms):
         if not self.has_hessian:
@@ -312,6 +334,33 @@ class Calculator:
     def get_hessian(self, atoms):
         """The same as an array (one download per geometry)."""
         hit = self._cached_hessian(atoms)
+        if hit[2] is None:
+            hit[2] = hit[1].numpy()
+        return hit[2].copy()
+
+    def _cached_cell_hessian(self, atoms):
+        if not self.has_cell_hessian:
+            raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian of positions and cell')
+        self._prepare(atoms)
+        key = cache_key(atoms)
+        hit = self._cell_hess
+        if hit is None or hit[0] != key or hit[1].ctx._h is None:                         # (or its context is gone)
+            if hit is not None:
+                hit[1].free()
+            self._cell_hess = None
+            cell = np.array(atoms.cell, dtype=np.float64)
+            self._cell_hess = [key, self.device_cell_hessian(atoms.positions, cell), None]
+            self.nhessians += 1
+        return self._cell_hess
+
+    def get_device_cell_hessian(self, atoms):
+        """The Hessian of positions and cell ((3N + 9) square, coordinates [positions; cell.ravel()], the positions fixed
+        while the lattice vectors vary) of the geometry of `atoms` as a `DeviceMatrix` of the caller's own."""
+        return self._cached_cell_hessian(atoms)[1].copy()
+
+    def get_cell_hessian(self, atoms):
+        """The same as an array (one download per geometry)."""
+        hit = self._cached_cell_hessian(atoms)
         if hit[2] is None:
             hit[2] = hit[1].numpy()
         return hit[2].copy()
@@ -484,7 +533,8 @@ class EMT(Calculator):
     along each periodic direction (one while the cell is at least a cutoff, ~5.3 A for Cu, wide), 127 images at most.
     get_stress() takes energy, forces and the virial from one device evaluation (`sella_emt_eval_stress`);
     get_hessian() / get_device_hessian() / hessian_vector_product() are the analytic second derivatives
-    (`sella_emt_hessian`, `sella_emt_hvp`)."""
+    (`sella_emt_hessian`, `sella_emt_hvp`), get_cell_hessian() / get_device_cell_hessian() those of positions and cell
+    together (`sella_emt_cell_hessian`)."""
     #              E0     s0    V0     eta2   kappa  lambda n0        (eV, bohr, eV, 1/bohr, 1/bohr, 1/bohr, 1/bohr^3)
     _PAR = dict(Al=(-3.28, 3.00, 1.493, 1.240, 2.000, 1.169, 0.00700), Cu=(-3.51, 2.67, 2.476, 1.652, 2.740, 1.906, 0.00910),
                 Ag=(-2.96, 3.01, 2.132, 1.652, 2.790, 1.892, 0.00547), Au=(-3.80, 3.00, 2.321, 1.674, 2.873, 2.182, 0.00703),
@@ -582,6 +632,13 @@ class EMT(Calculator):
     def hessian_products(self, pos, V):
         from .device import get_context
         return get_context().emt_hvp(*self._emt_args(pos), V)
+
+    def device_cell_hessian(self, pos, cell):
+        """The analytic Hessian of positions and cell (csrc/emt_hessian.hip: the cell enters through the image
+        translations, so the same pair quantities contracted with the image indices)."""
+        from .device import get_context
+        pos, par, shifts, *tail = self._emt_args(pos)
+        return get_context().emt_cell_hessian(pos, par, shifts, cell, *tail)
 
     library_form = True
 

@@ -779,6 +779,19 @@ int sella_mat_copy_into(sella_ctx* c, sella_mat src, sella_mat dst, int nrows) {
     return launch_axpby2d(c, nrows, s->cols, 1.0, s->d, s->ld, 0.0, nullptr, 0, d->d, d->ld);
 }
 
+// dst[drow + i][dcol + j] <- src[srow + i][scol + j], i < rows, j < cols   (src and dst different matrices)
+int sella_mat_copy_block(sella_ctx* c, sella_mat src, int srow, int scol, int rows, int cols, sella_mat dst, int drow,
+                         int dcol) {
+    Mat *s = mat_get(c, src), *d = mat_get(c, dst);
+    if (!s || !d || s == d || rows < 0 || cols < 0 || srow < 0 || scol < 0 || drow < 0 || dcol < 0 ||
+        srow > s->rows - rows || scol > s->cols - cols || drow > d->rows - rows || dcol > d->cols - cols) {
+        set_error("mat_copy_block: block outside a matrix");
+        return SELLA_E_INVALID;
+    }
+    return launch_axpby2d(c, rows, cols, 1.0, s->d + (size_t)srow * s->ld + scol, s->ld, 0.0, nullptr, 0,
+                          d->d + (size_t)drow * d->ld + dcol, d->ld);
+}
+
 // new matrix holding rows [row0, row0 + nrows) of src
 int sella_mat_rows(sella_ctx* c, sella_mat src, int row0, int nrows, sella_mat* dst) {
     Mat* s = mat_get(c, src);

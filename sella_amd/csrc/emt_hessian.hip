@@ -21,6 +21,23 @@
 // 256 divides N, so everything that lands in a shared place is added image by image with a barrier in between (one
 // writer per (i, j) within an image, images in index order); per-thread sums run in the order of the lists and are
 // reduced by block_sum.  The result does not depend on whether the lists were complete.
+//
+// The cell (sella_emt_cell_hessian).  The lattice vectors (rows of C) enter only through the image translations
+// S_s = n_s C, n_s whole numbers: for a visit d = x_j + n_s C - x_i, so dd_a / dC_kb = n_k delta_ab, and in the coordinates
+// [x; C.ravel()] (positions fixed while C varies) the same pair quantities give, with gamma_i = d sigma_i / dC,
+//     gamma_i[(k,b)]   = sum_visits of i  w'_ij u_b n_k
+//     A[(i,a),(k,b)]   = d2E / dx_ia dC_kb = - sum_visits of i, j != i  K_ab n_k  +  sum_m F2_m g_m[(i,a)] gamma_m[(k,b)]
+//     B[(k,a),(l,b)]   = d2E / dC_ka dC_lb = 1/2 sum_all visits  K_ab n_k n_l   +  sum_m F2_m gamma_m[(k,a)] gamma_m[(l,b)]
+// The pair term of B is sum over ORDERED pairs of their own K n_k n_l; a visit's K holds the ordered pairs (i <- j, s) and
+// (j <- i, -s), whose n_k n_l agree, and each of the two is met again in the visit from the other end: hence the 1/2.  A
+// visit of an atom to its own image s holds (i <- i, s) and (i <- i, -s), both met again in the visit to image -s: the
+// same 1/2.  Those visits move no position block (x_i - x_i cancels in d) but d = n_s C does depend on the cell, so the
+// cell pass — and only it — takes them (emt_pair<true>), for gamma_i and B.
+//   emt_hessian passes into the leading 3n x 3n block -> emt_cell_pair (per atom: the pair term of row block i of A, row i
+//   of gamma, atom i's share of B: 36 numbers, K_ab n_k n_l being symmetric in (a,b) and in (k,l)) -> emt_cell_embed (A +=
+//   (diag(F2) G^T)^T gamma) -> emt_cell_finish (B from the shares and gamma, summed in a fixed order; A^T into the last rows)
+#include <cmath>
+
 #include "emt.h"
 
 namespace sella {
@@ -64,10 +81,12 @@ struct EmtPair {                            // one visit (neighbour j through im
     double wp_ij, wp_ji;                    // dw/dr of (i <- j) and of (j <- i)
     double e1, e2;                          // first and second radial derivative of the energy of the two pairs
 };
-// false: not a pair (outside the cutoff, the atom itself, or the atom's own image)
+// false: not a pair (outside the cutoff, the atom itself, or the atom's own image).  SELF: the atom's own images are
+// pairs too (the cell pass: their distance depends on the cell); j = i, and both ordered pairs are (i <- i).
+template <bool SELF = false>
 __device__ __forceinline__ bool emt_pair(const EmtArgs& a, const EmtAtom& m, int t, EmtPair& p) {
     const int j = t & 0xffffff, s = t >> 24;
-    if (j == m.i) return false;
+    if (!SELF && j == m.i) return false;
     const double dx = a.pos[3 * j] + a.shifts[3 * s] - m.x;
     const double dy = a.pos[3 * j + 1] + a.shifts[3 * s + 1] - m.y;
     const double dz = a.pos[3 * j + 2] + a.shifts[3 * s + 2] - m.z;
@@ -260,9 +279,160 @@ __device__ __forceinline__ void emt_hvp_gather_vb(const VB vb, EmtArgs a, EmtHvp
 }
 __global__ __launch_bounds__(256) void emt_hvp_gather_kernel(EmtArgs a, EmtHvp o) { emt_hvp_gather_vb(vb_hw(), a, o); }
 
+// ---- the cell columns ---------------------------------------------------------------------------------------------------
+// symmetric index of (a, b), a, b in 0..2, in the order xx, yy, zz, yz, xz, xy
+__host__ __device__ __forceinline__ int sym6(int a, int b) { return a == b ? a : 6 - a - b; }
+
+struct EmtCell {
+    const double* F2;
+    const double* nimg;                     // nshift x 3: n_s = S_s C^-1, whole numbers
+    double* H; int ldh;                     // (3n + 9) square
+    double* gam; int ldgam;                 // n x 9: row i = gamma_i, column 3 k + b
+    double* share;                          // n x 36: atom i's share of the pair term of B, [sym6(k, l)][sym6(a, b)]
+};
+
+// Pair term of row block i of A (into columns 3n .. 3n + 8 of rows 3i .. 3i + 2 of H), row i of gamma, atom i's share of B.
+__device__ __forceinline__ void emt_cell_pair_vb(const VB vb, EmtArgs a, EmtCell o) {
+    __shared__ double part[4][63];
+    __shared__ int incomplete;
+    const int i = vb.x;
+    const EmtAtom m = emt_atom(a, i);
+    double kn[3][6], gk[3][3], kk[6][6];    // sum K n_k (j != i); sum w' u_b n_k; sum K n_k n_l
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) kn[k][q] = 0.0;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) gk[k][b] = 0.0;
+    }
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+#pragma unroll
+        for (int q = 0; q < 6; ++q) kk[p][q] = 0.0;
+    auto visit = [&](int t) {
+        const double* ns = o.nimg + 3 * (t >> 24);
+        const double nv[3] = {ns[0], ns[1], ns[2]};
+        if (nv[0] == 0.0 && nv[1] == 0.0 && nv[2] == 0.0) return;                 // the home image: no cell in d
+        EmtPair p;
+        if (!emt_pair<true>(a, m, t, p)) return;
+        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
+        const double K[6] = {c1 + c2 * (p.ux * p.ux), c1 + c2 * (p.uy * p.uy), c1 + c2 * (p.uz * p.uz),
+                             c2 * (p.uy * p.uz), c2 * (p.ux * p.uz), c2 * (p.ux * p.uy)};
+        const double wu[3] = {p.wp_ij * p.ux, p.wp_ij * p.uy, p.wp_ij * p.uz};
+        const double nn[6] = {nv[0] * nv[0], nv[1] * nv[1], nv[2] * nv[2], nv[1] * nv[2], nv[0] * nv[2], nv[0] * nv[1]};
+        const double other = p.j != i ? 1.0 : 0.0;                                // an own image moves no position block
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double nk = other * nv[k];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) kn[k][q] += K[q] * nk;
+#pragma unroll
+            for (int b = 0; b < 3; ++b) gk[k][b] += wu[b] * nv[k];
+        }
+#pragma unroll
+        for (int pq = 0; pq < 6; ++pq)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) kk[pq][q] += K[q] * nn[pq];
+    };
+    emt_by_image<false>(a, i, &incomplete, visit);
+    // block_sum's arithmetic for all 63 sums behind one barrier: the wavefronts' sums side by side in LDS, then thread
+    // t adds those of sum t and stores it
+    const int wave = threadIdx.x >> 6;
+    auto put = [&](int slot, double v) {
+        v = wave_sum64(v);
+        if ((threadIdx.x & 63) == 0) part[wave][slot] = v;
+    };
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) put(6 * k + q, kn[k][q]);
+#pragma unroll
+        for (int b = 0; b < 3; ++b) put(18 + 3 * k + b, gk[k][b]);
+    }
+#pragma unroll
+    for (int p = 0; p < 6; ++p)
+#pragma unroll
+        for (int q = 0; q < 6; ++q) put(27 + 6 * p + q, kk[p][q]);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= 63) return;
+    const double v = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+    if (t < 18) {                           // - sum K_rb n_k into A[(i, r), (k, b)], both (r, b) of an off-diagonal component
+        const int k = t / 6, q = t % 6, n3 = 3 * a.n;
+        for (int r = 0; r < 3; ++r)
+            for (int b = 0; b < 3; ++b)
+                if (sym6(r, b) == q) o.H[(size_t)(3 * i + r) * o.ldh + n3 + 3 * k + b] = -v;
+    } else if (t < 27) {
+        o.gam[(size_t)i * o.ldgam + (t - 18)] = v;
+    } else {
+        o.share[(size_t)i * 36 + (t - 27)] = 0.5 * v;
+    }
+}
+__global__ __launch_bounds__(256) void emt_cell_pair_kernel(EmtArgs a, EmtCell o) { emt_cell_pair_vb(vb_hw(), a, o); }
+
+// A += (diag(F2) G^T)^T gamma, 3n x 9 with inner dimension n, too thin for the tiles of launch_gemm: a workgroup takes 16
+// rows q of A (columns of Gs, n x 3n) and splits the inner index m over 16 slices (m = slice, slice + 16, ...: a
+// wavefront reads four 128-byte pieces of rows of Gs at a time); the slices meet in LDS and are added in index order.
+__device__ __forceinline__ void emt_cell_embed_vb(const VB vb, int n, const double* __restrict__ Gs, int ldg, EmtCell o) {
+    __shared__ double part[16][16][9];
+    const int ql = threadIdx.x & 15, sl = threadIdx.x >> 4;
+    const int n3 = 3 * n, q = vb.x * 16 + ql;
+    double acc[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) acc[c] = 0.0;
+    if (q < n3)
+        for (int m = sl; m < n; m += 16) {
+            const double g = Gs[(size_t)m * ldg + q];
+            const double* gm = o.gam + (size_t)m * o.ldgam;
+#pragma unroll
+            for (int c = 0; c < 9; ++c) acc[c] += g * gm[c];
+        }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) part[sl][ql][c] = acc[c];
+    __syncthreads();
+    if (threadIdx.x >= 144) return;
+    const int qo = vb.x * 16 + threadIdx.x / 9, c = threadIdx.x % 9;
+    if (qo >= n3) return;
+    double sum = 0.0;
+    for (int u = 0; u < 16; ++u) sum += part[u][threadIdx.x / 9][c];
+    o.H[(size_t)qo * o.ldh + n3 + c] += sum;
+}
+__global__ __launch_bounds__(256) void emt_cell_embed_kernel(int n, const double* __restrict__ Gs, int ldg, EmtCell o) {
+    emt_cell_embed_vb(vb_hw(), n, Gs, ldg, o);
+}
+
+// Workgroups 0 .. 44: entry (P, Q), P <= Q, of B = sum_i share_i + sum_i F2_i gamma_i gamma_i^T and its mirror image — every
+// thread adds its atoms (i = tid, tid + 256, ...) in increasing i, block_sum adds the threads: one fixed order.  The
+// workgroups behind them copy A (rows of the positions, last nine columns) into the last nine rows.
+__device__ __forceinline__ void emt_cell_finish_vb(const VB vb, int n, EmtCell o) {
+    __shared__ double red[4];
+    const int n3 = 3 * n;
+    if (vb.x >= 45) {
+        const int r = (vb.x - 45) * 256 + threadIdx.x;
+        if (r < n3)
+            for (int q = 0; q < 9; ++q) o.H[(size_t)(n3 + q) * o.ldh + r] = o.H[(size_t)r * o.ldh + n3 + q];
+        return;
+    }
+    int P = 0, rest = vb.x;                 // row P of the upper triangle holds 9 - P entries
+    while (rest >= 9 - P) { rest -= 9 - P; ++P; }
+    const int Q = P + rest;
+    const int w = 6 * sym6(P / 3, Q / 3) + sym6(P % 3, Q % 3);
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double* g = o.gam + (size_t)i * o.ldgam;
+        acc += o.share[(size_t)i * 36 + w] + o.F2[i] * g[P] * g[Q];
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) {
+        o.H[(size_t)(n3 + P) * o.ldh + n3 + Q] = acc;
+        o.H[(size_t)(n3 + Q) * o.ldh + n3 + P] = acc;
+    }
+}
+__global__ __launch_bounds__(256) void emt_cell_finish_kernel(int n, EmtCell o) { emt_cell_finish_vb(vb_hw(), n, o); }
+
 struct TempMats {                           // device matrices of one call, back to the pool on every way out (stream-ordered)
     sella_ctx* c;
-    sella_mat h[2] = {SELLA_NO_MAT, SELLA_NO_MAT};
+    sella_mat h[3] = {SELLA_NO_MAT, SELLA_NO_MAT, SELLA_NO_MAT};
     explicit TempMats(sella_ctx* ctx) : c(ctx) {}
     ~TempMats() {
         for (sella_mat m : h)
@@ -274,6 +444,23 @@ struct TempMats {                           // device matrices of one call, back
 }  // namespace sella
 
 using namespace sella;
+
+// The passes of the dense Hessian into the leading 3n x 3n block of H (rows ldh apart, zero on entry), symmetrised.
+// G^T and diag(F2) G^T (n x 3n) stay behind in t.h[0], t.h[1].
+static int emt_hessian_block(sella_ctx* c, int n, const EmtArgs& a, double* F2, double* H, int ldh, TempMats& t) {
+    SCHK(mat_new(c, n, 3 * n, &t.h[0]));                              // zeroed: the visits add into the rows
+    SCHK(mat_new(c, n, 3 * n, &t.h[1]));
+    Mat *Gt = mat_get(c, t.h[0]), *Gs = mat_get(c, t.h[1]);
+    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, F2);
+    EmtHessOut o;
+    o.F2 = F2; o.H = H; o.ldh = ldh; o.Gt = Gt->d; o.Gs = Gs->d; o.ldg = Gt->ld;
+    SELLA_LAUNCHB(c, emt_hess_pair_kernel, emt_hess_pair_vb, 256, dim3(n), dim3(256), 0, a, o);
+    HIPCHK(hipGetLastError());
+    // H += G diag(F2) G^T, G^T = Gt (n x 3n)
+    SCHK(launch_gemm(c, 1, 0, 3 * n, 3 * n, n, 1.0, Gt->d, Gt->ld, Gs->d, Gs->ld, 1.0, H, ldh));
+    // the two triangles agree to rounding only (x_j + shift - x_i from either end, the tiles of the product)
+    return launch_symmetrize(c, H, 3 * n, ldh);
+}
 
 // dconst as in emt_eval_resident.  `out` (3n x 3n) is overwritten and stays on the device.
 int sella::emt_hessian_resident(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
@@ -287,20 +474,79 @@ int sella::emt_hessian_resident(sella_ctx* c, int n, const double* pos, const do
     double* F2;
     SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, (size_t)n, &a, &F2));
     TempMats t(c);
-    SCHK(mat_new(c, n, 3 * n, &t.h[0]));                              // zeroed: the visits add into the rows
-    SCHK(mat_new(c, n, 3 * n, &t.h[1]));
-    H = mat_get(c, out);
-    Mat *Gt = mat_get(c, t.h[0]), *Gs = mat_get(c, t.h[1]);
     HIPCHK(s_memset0(c, H->d, (size_t)H->rows * H->ld * sizeof(double)));
-    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, F2);
-    EmtHessOut o;
-    o.F2 = F2; o.H = H->d; o.ldh = H->ld; o.Gt = Gt->d; o.Gs = Gs->d; o.ldg = Gt->ld;
-    SELLA_LAUNCHB(c, emt_hess_pair_kernel, emt_hess_pair_vb, 256, dim3(n), dim3(256), 0, a, o);
+    SCHK(emt_hessian_block(c, n, a, F2, H->d, H->ld, t));
+    return stream_wait(c);
+}
+
+// Image indices n_s = S_s C^-1 of the shifts in the cell (lattice vectors in the rows of C): whole numbers, or the
+// shifts are no lattice translations of this cell.
+static int emt_image_indices(const double* cell, int nshift, const double* shifts, std::vector<double>& nimg) {
+    const double* C = cell;
+    const double cof[9] = {C[4] * C[8] - C[5] * C[7], C[2] * C[7] - C[1] * C[8], C[1] * C[5] - C[2] * C[4],
+                           C[5] * C[6] - C[3] * C[8], C[0] * C[8] - C[2] * C[6], C[2] * C[3] - C[0] * C[5],
+                           C[3] * C[7] - C[4] * C[6], C[1] * C[6] - C[0] * C[7], C[0] * C[4] - C[1] * C[3]};   // adj(C)
+    const double det = C[0] * cof[0] + C[1] * cof[3] + C[2] * cof[6];
+    double scale = 1.0;
+    for (int k = 0; k < 3; ++k) scale *= std::sqrt(C[3 * k] * C[3 * k] + C[3 * k + 1] * C[3 * k + 1] + C[3 * k + 2] * C[3 * k + 2]);
+    if (!std::isfinite(det) || !(std::fabs(det) > 1e-12 * scale)) {
+        set_error("emt_cell_hessian: the cell is singular (determinant %g)", det);
+        return SELLA_E_INVALID;
+    }
+    nimg.resize((size_t)3 * nshift);
+    for (int s = 0; s < nshift; ++s)
+        for (int k = 0; k < 3; ++k) {
+            const double* S = shifts + 3 * s;
+            const double v = (S[0] * cof[k] + S[1] * cof[3 + k] + S[2] * cof[6 + k]) / det;
+            const double w = std::nearbyint(v);
+            if (!(std::fabs(v - w) <= 1e-6)) {
+                set_error("emt_cell_hessian: shift %d is no lattice translation of the cell (index %g along vector %d)", s, v, k);
+                return SELLA_E_INVALID;
+            }
+            nimg[(size_t)3 * s + k] = w;
+        }
+    return SELLA_OK;
+}
+
+extern "C" int sella_emt_cell_hessian(sella_ctx* c, int n, const double* pos, const double* par /* 9 x n */, int nshift,
+                                      const double* shifts, const double* cell, double rc, double acut, double cutoff,
+                                      double beta, sella_mat out) {
+    if (!c || n <= 0 || !pos || !par || nshift <= 0 || !shifts || !cell) {
+        set_error("emt_cell_hessian: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    const int n3 = 3 * n, dim = n3 + 9;
+    Mat* H = mat_get(c, out);
+    if (!H || H->rows != dim || H->cols != dim) {
+        set_error("emt_cell_hessian: out must be the %d x %d matrix of %d atoms and the cell", dim, dim, n);
+        return SELLA_E_INVALID;
+    }
+    if (nshift > 127) { set_error("emt: at most 2^24 atoms and 127 periodic images"); return SELLA_E_INVALID; }
+    std::vector<double> nimg;
+    SCHK(emt_image_indices(cell, nshift, shifts, nimg));
+    EmtArgs a;
+    double* ex;                                                       // F2 (n), image indices (3 nshift), shares of B (36 n)
+    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta,
+                           (size_t)n + (size_t)3 * nshift + (size_t)36 * n, &a, &ex));
+    double* dn = ex + n;
+    SCHK(h2d_async(c, dn, nimg.data(), nimg.size() * sizeof(double)));
+    TempMats t(c);
+    H = mat_get(c, out);
+    HIPCHK(s_memset0(c, H->d, (size_t)H->rows * H->ld * sizeof(double)));
+    // the 3n x 3n block: the passes of sella_emt_hessian, only the row stride differs
+    SCHK(emt_hessian_block(c, n, a, ex, H->d, H->ld, t));
+    SCHK(mat_new(c, n, 9, &t.h[2]));
+    H = mat_get(c, out);
+    Mat *Gs = mat_get(c, t.h[1]), *gam = mat_get(c, t.h[2]);
+    EmtCell o;
+    o.F2 = ex; o.nimg = dn; o.H = H->d; o.ldh = H->ld; o.gam = gam->d; o.ldgam = gam->ld; o.share = dn + (size_t)3 * nshift;
+    SELLA_LAUNCHB(c, emt_cell_pair_kernel, emt_cell_pair_vb, 256, dim3(n), dim3(256), 0, a, o);
     HIPCHK(hipGetLastError());
-    // H += G diag(F2) G^T, G^T = Gt (n x 3n)
-    SCHK(launch_gemm(c, 1, 0, 3 * n, 3 * n, n, 1.0, Gt->d, Gt->ld, Gs->d, Gs->ld, 1.0, H->d, H->ld));
-    // the two triangles agree to rounding only (x_j + shift - x_i from either end, the tiles of the product)
-    SCHK(launch_symmetrize(c, H->d, 3 * n, H->ld));
+    // A += G diag(F2) gamma: (diag(F2) G^T)^T (3n x n) times gamma (n x 9)
+    SELLA_LAUNCHB(c, emt_cell_embed_kernel, emt_cell_embed_vb, 256, dim3((n3 + 15) / 16), dim3(256), 0, n,
+                  (const double*)Gs->d, Gs->ld, o);
+    SELLA_LAUNCHB(c, emt_cell_finish_kernel, emt_cell_finish_vb, 256, dim3(45 + (n3 + 255) / 256), dim3(256), 0, n, o);
+    HIPCHK(hipGetLastError());
     return stream_wait(c);
 }
 

@@ -469,6 +469,11 @@ class Context:
     def mat_copy_into(self, src, dst, nrows):
         check(_lib.lib().sella_mat_copy_into(self._h, src.handle, dst.handle, int(nrows)))
 
+    def mat_copy_block(self, src, srow, scol, rows, cols, dst, drow, dcol):
+        """dst[drow:drow + rows, dcol:dcol + cols] = src[srow:srow + rows, scol:scol + cols] on the device."""
+        check(_lib.lib().sella_mat_copy_block(self._h, src.handle, int(srow), int(scol), int(rows), int(cols), dst.handle,
+                                              int(drow), int(dcol)))
+
     def mat_add_diag(self, M, alpha):
         check(_lib.lib().sella_mat_add_diag(self._h, M.handle, float(alpha)))
 
@@ -635,6 +640,25 @@ class Context:
         out = self.zeros(3 * n, 3 * n)
         check(_lib.lib().sella_emt_hessian(self._h, n, ptr(pos), ptr(par), shifts.shape[0], ptr(shifts), float(rc),
                                            float(acut), float(cutoff), float(beta), out.handle))
+        return out
+
+    def emt_cell_hessian(self, pos, par, shifts, cell, rc, acut, cutoff, beta):
+        """The analytic Hessian of positions and cell of the EMT potential as a (3n + 9)-square `DeviceMatrix`
+        (`sella_emt_cell_hessian`), in the coordinates [positions; cell.ravel()] with the positions fixed while the
+        lattice vectors (rows of `cell`) vary; `shifts` must be lattice translations of `cell`.  Exactly symmetric, its
+        leading 3n x 3n block bit for bit `emt_hessian`'s, left on the device."""
+        pos = as_f64(pos)
+        par = as_f64(par)
+        shifts = as_f64(shifts)
+        cell = as_f64(cell, (3, 3))
+        n = pos.shape[0]
+        out = self.zeros(3 * n + 9, 3 * n + 9)
+        try:
+            check(_lib.lib().sella_emt_cell_hessian(self._h, n, ptr(pos), ptr(par), shifts.shape[0], ptr(shifts), ptr(cell),
+                                                    float(rc), float(acut), float(cutoff), float(beta), out.handle))
+        except Exception:
+            out.free()
+            raise
         return out
 
     def emt_hvp(self, pos, par, shifts, rc, acut, cutoff, beta, V):

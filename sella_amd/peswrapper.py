@@ -1123,7 +1123,10 @@ class CellCartesianPES(PES):
     exp_cell_factor (default N) scales the log-deformation; cell_mask (3 x 3 bools, default all) selects the free
     entries; scalar_pressure (eV / A^3) adds p V to the energy.  The initial Hessian is the user's H0, else 70 I on the
     positions and 1 I on the cell; refine_initial_hessian fills the cell columns by central differences (2 n_cell_dof
-    evaluations, step hessian_delta); save_hessian names an .npy file for it."""
+    evaluations, step hessian_delta; not run with a hessian_function); save_hessian names an .npy file for it.
+    hessian_function(atoms) returns the (3N + 9)-square Hessian in the coordinates [positions; cell.ravel()] (lattice
+    vectors in the rows of the cell, positions fixed while the cell varies), as an array or a `DeviceMatrix`, e.g.
+    `EMT.get_device_cell_hessian`; `calculate_hessian` carries it into the PES's own coordinates."""
 
     def __init__(self, atoms, H0=None, constraints=None, eigensolver='jd0', trajectory=None, eta=1e-4, v0=None,
                  proj_trans=None, proj_rot=None, hessian_function=None, exp_cell_factor=None, cell_mask=None,
@@ -1147,7 +1150,8 @@ class CellCartesianPES(PES):
         else:
             H0 = np.eye(self.dim)
             H0[:nc, :nc] *= 70.0
-            if refine_initial_hessian:
+            # (with a hessian_function the exact Hessian replaces H0 at the first step: no finite differences for it)
+            if refine_initial_hessian and hessian_function is None:
                 cols = self._cell_hessian_columns(hessian_delta)
                 H0[:nc, nc:] = cols[:nc]
                 H0[nc:, :nc] = cols[:nc].T
@@ -1225,17 +1229,120 @@ class CellCartesianPES(PES):
         self.write_traj()
         return f, g
 
-    def _cell_gradient(self, stress, forces):
+    def _dEdC(self, stress, forces):
+        """(dE/dC (3 x 3, p V included) at fixed Cartesian positions, C) from the stress and the forces."""
         sigma = voigt_to_matrix(stress) if np.size(stress) == 6 else np.asarray(stress, dtype=np.float64).reshape(3, 3)
         sigma = sigma + self.scalar_pressure * np.eye(3)
         C = self._cell()
         volume = abs(np.linalg.det(C))
         pos = np.asarray(self.atoms.positions, dtype=np.float64)
-        dEdC = np.linalg.solve(C.T, volume * sigma + pos.T @ forces)     # at fixed Cartesian positions
+        return np.linalg.solve(C.T, volume * sigma + pos.T @ forces), C
+
+    def _cell_gradient(self, stress, forces):
+        dEdC, C = self._dEdC(stress, forces)
         dEdF = dEdC @ self.orig_cell.T                                   # C = F C0
         U = logm_3x3(C @ np.linalg.inv(self.orig_cell))
         g = expm_frechet_3x3_contracted(U, dEdF)
         return g[self.cell_mask] / self.exp_cell_factor
+
+    # ---- exact Hessians: hessian_function in the coordinates [x; C.ravel()] -------------------------------------
+    def _expm_derivatives(self, U):
+        """(D1 (m, 3, 3), D2 (m, m, 3, 3)): the first and second Frechet derivatives D expm(U)[E_m] and
+        D2 expm(U)[E_m, E_q] along the masked unit directions, from one 9 x 9 exponential per ordered pair: in
+        expm([[U, E1, 0], [0, U, E2], [0, 0, U]]) the (1,2) block is D expm(U)[E1] and the (1,3) block the E1-before-E2
+        half of the second derivative, which is that block plus the one with E1 and E2 swapped."""
+        dirs = []
+        for r, c in zip(*np.nonzero(self.cell_mask)):                    # row-major, the order of L[cell_mask]
+            E = np.zeros((3, 3))
+            E[r, c] = 1.0
+            dirs.append(E)
+        m = len(dirs)
+        D1, half = np.zeros((m, 3, 3)), np.zeros((m, m, 3, 3))
+        big = np.zeros((9, 9))
+        for k in range(3):
+            big[3 * k:3 * k + 3, 3 * k:3 * k + 3] = U
+        for i, E1 in enumerate(dirs):
+            for j, E2 in enumerate(dirs):
+                big[0:3, 3:6], big[3:6, 6:9] = E1, E2
+                X = expm(big)
+                half[i, j] = X[0:3, 6:9]
+                if j == 0:
+                    D1[i] = X[0:3, 3:6]
+        return D1, half + half.transpose(1, 0, 2, 3)
+
+    def _cell_block_to_params(self, rows):
+        """The cell rows of the Hessian in the PES's own coordinates, (m, 3N + m), from the nine cell rows `rows`
+        (9, 3N + 9) of the Hessian in [x; C.ravel()].  With U = L / exp_cell_factor, C = expm(U) C0 and the masked unit
+        directions E_m: J[:, m] = vec(D expm(U)[E_m] C0) / exp_cell_factor, H_px = J^T H_Cx, and
+        H_pp = J^T H_CC J + sum_ab dEdC_ab (D2 expm(U)[E_m, E_q] C0)_ab / exp_cell_factor^2; p V adds
+        p d2|det C|/dC2 to H_CC first (its first derivative is part of dEdC)."""
+        nc, fac = self.ncart, self.exp_cell_factor
+        stress = np.asarray(self.atoms.get_stress(), dtype=np.float64)
+        forces = np.asarray(self.atoms.get_forces(), dtype=np.float64).reshape((-1, 3))
+        dEdC, C = self._dEdC(stress, forces)
+        H_Cx, H_CC = rows[:, :nc], rows[:, nc:].copy()
+        if self.scalar_pressure != 0.0:
+            Ci = np.linalg.inv(C)
+            # d2 det C / dC_ab dC_cd = det C (C^-1_ba C^-1_dc - C^-1_da C^-1_bc)
+            d2 = np.einsum('ba,dc->abcd', Ci, Ci) - np.einsum('da,bc->abcd', Ci, Ci)
+            H_CC += self.scalar_pressure * abs(np.linalg.det(C)) * d2.reshape(9, 9)
+        U = logm_3x3(C @ np.linalg.inv(self.orig_cell))
+        D1, D2 = self._expm_derivatives(U)
+        J = (D1 @ self.orig_cell).reshape(len(D1), 9).T / fac             # (9, m)
+        dEdF = dEdC @ self.orig_cell.T
+        H_pp = J.T @ H_CC @ J + np.einsum('ab,mqab->mq', dEdF, D2) / fac ** 2
+        return np.hstack([J.T @ H_Cx, 0.5 * (H_pp + H_pp.T)])
+
+    def _convert_cell_hessian(self, H, consume=False):
+        """The Hessian in the PES's coordinates [x; p] of what a `hessian_function` returns in a cell run: the
+        (3N + 9)-square Hessian in [x; C.ravel()] (lattice vectors in the rows of C, positions fixed while C varies), as
+        an array or a `DeviceMatrix`; the result is of the same kind.  The 3N x 3N block is carried over as it is — on the
+        device it never leaves it: only the nine cell rows are taken to the host, transformed there and sent back.
+        `consume` hands a `DeviceMatrix` over (freed here)."""
+        from .device import DeviceMatrix
+        nc, m = self.ncart, self.n_cell_dof
+        on_device = isinstance(H, DeviceMatrix)
+        if not on_device:
+            H = np.asarray(H, dtype=np.float64)
+        if H.shape != (nc + 9, nc + 9):
+            shape = ' x '.join(str(k) for k in H.shape)
+            if on_device and consume:
+                H.free()
+            hint = (f': {nc} x {nc} is the Hessian at fixed cell; a cell run needs the (3N+9)-square one, e.g. '
+                    f'`calc.get_device_cell_hessian`') if H.shape == (nc, nc) else ''
+            raise ValueError(f'hessian_function must return the {nc + 9} x {nc + 9} Hessian of the {len(self.atoms)} atoms '
+                             f'and the nine cell entries in a cell run, got {shape}{hint}')
+        if not on_device:
+            low = self._cell_block_to_params(H[nc:])
+            out = np.empty((nc + m, nc + m))
+            out[:nc, :nc] = H[:nc, :nc]
+            out[nc:] = low
+            out[:nc, nc:] = low[:, :nc].T
+            return out
+        ctx = H.ctx
+        rows = ctx.mat_rows(H, nc, 9)
+        try:
+            low = self._cell_block_to_params(rows.numpy())
+        finally:
+            rows.free()
+        out = ctx.zeros(nc + m, nc + m)
+        hlow = ctx.upload(low)
+        hcol = hlow.transpose()
+        try:
+            ctx.mat_copy_block(H, 0, 0, nc, nc, out, 0, 0)
+            ctx.mat_copy_block(hlow, 0, 0, m, nc + m, out, nc, 0)
+            ctx.mat_copy_block(hcol, 0, 0, nc, m, out, 0, nc)
+        finally:
+            hlow.free()
+            hcol.free()
+            if consume:
+                H.free()
+        return out
+
+    def calculate_hessian(self):
+        assert self.hessian_function is not None
+        # what the hessian_function returns is the PES's from here on, as in `PES.calculate_hessian`
+        self.H.set_B(self._convert_cell_hessian(self.hessian_function(self.atoms), consume=True))
 
     # ---- constraints: they act on the positions only ------------------------------------------------------------
     def get_drdx(self):

@@ -5,13 +5,18 @@ Hessian they replace; prints one JSON line.
     python tools/emt_hessian_bench.py [--reps R] [--warmup W] [--k K] [--fd-columns C] [--out FILE]
 
 On the 1024-atom Cu(111) slab of bench.py (9 periodic images), host clock around calls that end in a stream
-synchronisation, all four alternated in one process after a warm-up of each:
+synchronisation, all of them alternated in one process after a warm-up of each:
 
   force_ms        one `sella_emt_eval` (upload, density and force pass, read-back)
   hessian_ms      one `sella_emt_hessian` (density pass, F2, pair blocks + G, rank-N product, symmetrisation; the result
                   stays on the device), and its parts from the library's own launch profile: the product
                   (`gemm_ms`, PROF_GEMM) against everything else
   hvp_ms          one `sella_emt_hvp` with K vectors (upload of V, three passes, read-back of H V)
+  cell_hessian_ms one `sella_emt_cell_hessian` (the passes of the Hessian into the (3N + 9)-wide result, then the cell
+                  pass, the 3N x N x 9 product and the finishing launch); `cell_over_hessian` is its ratio to
+                  hessian_ms of the same run
+  refine_ms       the 18 `sella_emt_eval_stress` calls that `refine_initial_hessian` spends on the nine cell columns
+                  (central differences of force + stress), as one sample
   fd_hessian_ms   the central-difference Hessian: 2 x 3N calls of `sella_emt_eval` at displaced geometries, the
                   difference quotients written into a host array, symmetrised and uploaded.  With --fd-columns C < 3N
                   only C columns are measured and the total is C-column time x 3N / C (the calls are identical in
@@ -57,7 +62,17 @@ def main():
     def hessian():
         ctx.emt_hessian(pos, *args).free()
 
-    calls = dict(force=lambda: ctx.emt_eval(pos, *args), hessian=hessian, hvp=lambda: ctx.emt_hvp(pos, *args, V))
+    cell = np.array(slab.cell, dtype=np.float64)
+
+    def cell_hessian():
+        ctx.emt_cell_hessian(pos, args[0], args[1], cell, *args[2:]).free()
+
+    def refine():
+        for _ in range(18):
+            ctx.emt_eval_stress(pos, *args)
+
+    calls = dict(force=lambda: ctx.emt_eval(pos, *args), hessian=hessian, hvp=lambda: ctx.emt_hvp(pos, *args, V),
+                 cell_hessian=cell_hessian, refine=refine)
     for fn in calls.values():
         for _ in range(a.warmup):
             fn()
@@ -114,6 +129,8 @@ def main():
     out['hvp_over_force'] = out['hvp_ms'] / out['force_ms']
     out['hessian_over_force'] = out['hessian_ms'] / out['force_ms']
     out['fd_over_hessian'] = out['fd_hessian_ms'] / out['hessian_ms']
+    out['cell_over_hessian'] = out['cell_hessian_ms'] / out['hessian_ms']
+    out['cell_over_hessian_min'] = out['cell_hessian_ms_min'] / out['hessian_ms_min']
     print(json.dumps(out), flush=True)
     if a.out:
         with open(a.out, 'w') as f:
