@@ -135,6 +135,8 @@ int sella_mgs(sella_ctx* ctx, const double* X, int n, int nx, const double* Y, i
  * A: resident dense matrix, or SELLA_NO_MAT with a callback (the finite-difference
  *    operator NumericalHessian, sella/linalg.py:39-95, lives behind the calculator boundary:
  *    a host-language callback for an ASE calculator, sella_fd_matvec for one of the library's own).
+ *    A third kind, the analytic Hessian-vector operator of a calculator of the library, stays on the device:
+ *    sella_davidson_hvp, declared with sella_hvp_* below.
  * P: given by its eigendecomposition P = Q diag(pevals) Q^T with Q resident both as columns
  *    (Pvecs) and as rows (PvecsT) — exactly what sella_eigh returns — or Pvecs = SELLA_NO_MAT
  *    for P = pscale * I.
@@ -532,6 +534,37 @@ int sella_fd_npairs(sella_fd* fd);
 long sella_fd_calls(sella_fd* fd);
 int sella_fd_pairs(sella_fd* fd, double* Vs, double* AVs);
 int sella_fd_destroy(sella_fd* fd);
+/* The same operator in closed form, for a calculator that has its second derivatives (sella_calc_hvp): H v exactly, no
+ * displacement, no force call (sella_calc_ncalls is unchanged).  What depends on the geometry x0 is built ONCE at creation
+ * and stays resident in an allocation of the operator's own — emt: one density pass and the second derivatives of the
+ * embedding functions (positions, densities, neighbour lists); model: the rows 2 c (u_j . x0) u_j — so a product is two
+ * launches on one device vector (emt; model: two row-panel matvecs) plus one that spreads the m free entries idx[0..m)
+ * (ascending; NULL: all n) over the full space.  The product is (H vfull)[idx] with vfull zero on the pinned coordinates.
+ *   sella_hvp_matvec     the sella_matvec_fn form with HOST vectors (upload, the device product, download, wait): the
+ *                        operator also serves the unchanged sella_davidson as its callback.
+ *   sella_davidson_hvp   sella_davidson with this operator as a third operator kind next to the resident matrix and the
+ *                        host callback: the iteration hands the operator the device addresses of its vector and of the
+ *                        product; no copy, no wait and no callback frame per product.  Arguments from Pvecs on as
+ *                        sella_davidson's (n: the operator's m); same synchronous iteration, same results as
+ *                        sella_davidson over sella_hvp_matvec.
+ * Every product of a non-vanishing vector is remembered, vfull and H vfull in full length (pinned rows included), on the
+ * device in chunks that are added as products arrive; sella_hvp_pairs returns them like sella_fd_pairs, (n x k) row-major,
+ * k = sella_hvp_npairs.  |v| < 1e-12 gives a zero product, counts as a call (sella_hvp_calls) and is not recorded.
+ * The operator must be destroyed before its calculator and context.  SELLA_E_INVALID: a null pointer, n != sella_calc_dim,
+ * m <= 0 or m > n with idx given, idx not ascending, an m (sella_hvp_matvec) / n (sella_davidson_hvp) that is not the
+ * operator's.                                                                                                            */
+typedef struct sella_hvp sella_hvp;
+int sella_hvp_create(sella_calc* calc, int n, const double* x0, const int* idx, int m, sella_hvp** op);
+int sella_hvp_matvec(void* op, const double* v, double* Av, int m);
+int sella_hvp_npairs(sella_hvp* op);
+long sella_hvp_calls(sella_hvp* op);
+int sella_hvp_pairs(sella_hvp* op, double* Vs, double* AVs);
+int sella_hvp_destroy(sella_hvp* op);
+int sella_davidson_hvp(sella_ctx* ctx, sella_hvp* op,
+                       sella_mat Pvecs, sella_mat PvecsT, const double* pevals, double pscale,
+                       int n, const double* v0, int nv0, double gamma, int method, int maxiter,
+                       const double* vref, double vreftol,
+                       double* lams, double* V, double* AV, int* k, int* nmatvec);
 
 /* ---- a whole search in the library --------------------------------------------------------------------------- */
 /* `Sella(atoms, ...).run(fmax, steps)` (sella/optimize/optimize.py:42-440 under ASE's Optimizer.irun) for the

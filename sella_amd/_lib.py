@@ -128,6 +128,15 @@ SIGNATURES = {
     'sella_fd_calls': (c_long, [c_void_p]),
     'sella_fd_pairs': (c_int, [c_void_p, c_void_p, c_void_p]),
     'sella_fd_destroy': (c_int, [c_void_p]),
+    'sella_hvp_create': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+    'sella_hvp_matvec': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    'sella_hvp_npairs': (c_int, [c_void_p]),
+    'sella_hvp_calls': (c_long, [c_void_p]),
+    'sella_hvp_pairs': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'sella_hvp_destroy': (c_int, [c_void_p]),
+    'sella_davidson_hvp': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                   c_double, c_int, c_void_p, c_int, c_double, c_int, c_int, c_void_p,
+                                   c_double, c_void_p, c_void_p, c_void_p, c_int_p, c_int_p]),
     'sella_search_create': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(SearchParams),
                                     POINTER(c_void_p)]),
     'sella_search_seed': (c_int, [c_void_p, c_double, c_void_p]),

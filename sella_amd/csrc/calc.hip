@@ -8,8 +8,13 @@
 //   sella_calc_emt_*     effective-medium theory (emt.hip, sella_emt_eval)
 //   sella_fd_*           H v ~ (g(x0 + eta v^) - g0) / eta (or the central form), seen through a selection of free
 //                        coordinates; every product is remembered as a secant pair for the Hessian update afterwards
-#include "internal.h"
+//   sella_hvp_*          H v in closed form (EMT: emt_hessian.hip; model: A v + sum_j 2 c (u_j . x0)(u_j . v) u_j) through the
+//                        same selection, on a state built once at x0 and owned by the operator: device vector in, device
+//                        vector out, no host wait per product (the third operator kind of sella_davidson, davidson.hip);
+//                        the pairs are recorded on the device.  Not force calls.
+#include "emt.h"
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -54,6 +59,53 @@ __device__ __forceinline__ void model_grad_vb(const VB vb, int n, int nu, int ld
 __global__ __launch_bounds__(256) void model_grad_kernel(int n, int nu, int ld, double cc, const double* __restrict__ Ax,
                                                          const double* __restrict__ p, const double* __restrict__ U,
                                                          double* __restrict__ g) { model_grad_vb(vb_hw(), n, nu, ld, cc, Ax, p, U, g); }
+
+// The eigensolver's vector x (its entry inv[p] belongs to full coordinate p; -1: pinned, zero; inv null: all free) as a
+// full-length row of the pair record, and |v|^2 of this workgroup's 256 entries into part[workgroup]
+__device__ __forceinline__ void hvp_scatter_vb(const VB vb, int n, const double* __restrict__ x, const int* __restrict__ inv,
+                                               double* __restrict__ vfull, double* __restrict__ part) {
+    __shared__ double red[4];
+    const int p = vb.x * 256 + threadIdx.x;
+    double v = 0.0;
+    if (p < n) {
+        const int q = inv ? inv[p] : p;
+        if (q >= 0) v = x[q];
+        vfull[p] = v;
+    }
+    const double s = block_sum(v * v, red);
+    if (threadIdx.x == 0) part[vb.x] = s;
+}
+__global__ __launch_bounds__(256) void hvp_scatter_kernel(int n, const double* __restrict__ x, const int* __restrict__ inv,
+                                                          double* __restrict__ vfull, double* __restrict__ part) { hvp_scatter_vb(vb_hw(), n, x, inv, vfull, part); }
+
+// Model kind: hv = A v (there already) + sum_j t_j S_j, S_j = 2 c (u_j . x0) u_j, t = U v, the rows taken in order; a
+// vanishing vector (|v| < 1e-12 from the partial sums) gives zero and flag 0; the free rows also go into y
+__device__ __forceinline__ void hvp_model_finish_vb(const VB vb, int n, int nu, int ld, const double* __restrict__ S,
+                                                    const double* __restrict__ t, const double* __restrict__ part, int nb,
+                                                    const int* __restrict__ inv, double* __restrict__ hv, double* __restrict__ y,
+                                                    int* __restrict__ flag) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 256) s += part[b];
+    s = block_sum(s, red);
+    const bool live = !(sqrt(s) < 1e-12);
+    if (vb.x == 0 && threadIdx.x == 0) *flag = live ? 1 : 0;
+    const int p = vb.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    double h = hv[p];
+    for (int j = 0; j < nu; ++j) h += t[j] * S[(size_t)j * ld + p];
+    if (!live) h = 0.0;
+    hv[p] = h;
+    const int q = inv ? inv[p] : p;
+    if (q >= 0) y[q] = h;
+}
+__global__ __launch_bounds__(256) void hvp_model_finish_kernel(int n, int nu, int ld, const double* __restrict__ S,
+                                                               const double* __restrict__ t, const double* __restrict__ part, int nb,
+                                                               const int* __restrict__ inv, double* __restrict__ hv, double* __restrict__ y,
+                                                               int* __restrict__ flag) { hvp_model_finish_vb(vb_hw(), n, nu, ld, S, t, part, nb, inv, hv, y, flag); }
 }  // namespace
 
 extern "C" int sella_calc_model_create(sella_ctx* c, sella_mat A, const double* U, int nu, int n, double cc, sella_calc** out) {
@@ -355,5 +407,200 @@ extern "C" int sella_fd_pairs(sella_fd* o, double* Vs, double* AVs) {
 
 extern "C" int sella_fd_destroy(sella_fd* o) {
     delete o;
+    return SELLA_OK;
+}
+
+// ---- analytic Hessian-vector operator ---------------------------------------------------------------------------------------
+// The pair record lives on the device in chunks of HVP_CHUNK products that are added as products arrive (never sized by
+// the eigensolver's iteration limit): rows [0, HVP_CHUNK) the full-space vectors, rows [HVP_CHUNK, 2 HVP_CHUNK) their
+// products, ld apart and zero beyond n, then one int per product: 1 recorded, 0 a vanishing vector.  Product number k (from
+// zero, vanishing ones included) owns row k mod HVP_CHUNK of chunk k / HVP_CHUNK, so the kernels write where the record
+// wants the result and the host learns which rows count when it asks for the pairs.
+constexpr int HVP_CHUNK = 16;
+
+struct sella_hvp {
+    sella_calc* calc = nullptr;
+    int n = 0, m = 0, ld = 0, nb = 0;     // full dimension, the eigensolver's, row stride, workgroups of the scatter
+    bool select = false;
+    EmtHvpState emt;                      // EMT kind
+    double* aux = nullptr;                // part (nb) | x, y of the host entry (ld each) | model: S (nu x ld), t | inv (n ints)
+    size_t aux_bytes = 0, chunk_bytes = 0;
+    double *part = nullptr, *dx = nullptr, *dy = nullptr, *S = nullptr, *t = nullptr;
+    int* inv = nullptr;
+    std::vector<double*> chunks;
+    std::vector<int> flags;               // host copy, valid for the first `nflags` products
+    long calls = 0;
+};
+
+static void hvp_release(sella_hvp* o) {
+    sella_ctx* c = o->calc->c;
+    (void)stream_sync_raw(c);
+    if (o->calc->kind == 1) emt_hvp_state_destroy(c, &o->emt);
+    for (double* p : o->chunks) dev_free(c, p, o->chunk_bytes);
+    if (o->aux) dev_free(c, o->aux, o->aux_bytes);
+    delete o;
+}
+
+extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const int* idx, int m, sella_hvp** out) {
+    if (!calc || !out || !x0 || n <= 0 || calc->n != n || (idx && (m <= 0 || m > n))) {
+        set_error("hvp operator: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    if (idx)
+        for (int q = 0; q < m; ++q)
+            if (idx[q] < 0 || idx[q] >= n || (q > 0 && idx[q] <= idx[q - 1])) {
+                set_error("hvp operator: the free coordinates must be ascending indices below %d", n);
+                return SELLA_E_INVALID;
+            }
+    sella_ctx* c = calc->c;
+    const int nu = calc->kind == 0 ? calc->nu : 0;
+    if (calc->kind == 0 && !mat_get(c, calc->A)) {
+        set_error("hvp operator: the model calculator's matrix A is gone");
+        return SELLA_E_INVALID;
+    }
+    sella_hvp* o = new sella_hvp();
+    o->calc = calc; o->n = n; o->m = idx ? m : n; o->select = idx != nullptr;
+    o->ld = round_up(n, 8);
+    o->nb = (n + 255) / 256;
+    const size_t ld = (size_t)o->ld, ldp = (size_t)round_up(nu > 0 ? nu : 1, 8), nbp = (size_t)round_up(o->nb, 8);
+    const size_t words = nbp + 2 * ld + (size_t)nu * ld + ldp + (ld + 1) / 2;
+    o->aux_bytes = words * sizeof(double);
+    o->chunk_bytes = ((size_t)2 * HVP_CHUNK * ld + HVP_CHUNK) * sizeof(double);
+    auto fail = [&](int st) { hvp_release(o); return st; };
+    int st = dev_alloc(c, o->aux_bytes, &o->aux);
+    if (st != SELLA_OK) { o->aux = nullptr; return fail(st); }
+    if (s_memset0(c, o->aux, o->aux_bytes) != hipSuccess) return fail(SELLA_E_HIP);
+    o->part = o->aux; o->dx = o->part + nbp; o->dy = o->dx + ld; o->S = o->dy + ld; o->t = o->S + (size_t)nu * ld;
+    if (idx) {
+        std::vector<int> inv((size_t)n, -1);
+        for (int q = 0; q < m; ++q) inv[idx[q]] = q;
+        o->inv = reinterpret_cast<int*>(o->t + ldp);
+        st = h2d_async(c, o->inv, inv.data(), (size_t)n * sizeof(int));
+        if (st != SELLA_OK) return fail(st);
+    }
+    if (calc->kind == 1) {
+        st = emt_hvp_state_create(c, calc->natoms, x0, calc->par.data(), calc->nshift, calc->shifts.data(), calc->dconst, calc->rc,
+                                  calc->acut, calc->cutoff, calc->beta, &o->emt);
+    } else {
+        if (nu > 0) {
+            std::vector<double> S((size_t)nu * ld, 0.0);               // rows 2 c (u_j . x0) u_j, as sella_calc_hessian builds them
+            for (int j = 0; j < nu; ++j) {
+                const double* u = calc->U.data() + (size_t)j * n;
+                double p = 0.0;
+                for (int i = 0; i < n; ++i) p += u[i] * x0[i];
+                for (int i = 0; i < n; ++i) S[(size_t)j * ld + i] = 2.0 * calc->cc * p * u[i];
+            }
+            st = h2d_async(c, o->S, S.data(), S.size() * sizeof(double));
+        }
+        if (st == SELLA_OK) st = stream_wait(c);
+    }
+    if (st != SELLA_OK) return fail(st);
+    *out = o;
+    return SELLA_OK;
+}
+
+// y (m entries) = (H vfull)[free], x (m entries) the free entries of vfull, both on the device: queued on the context's
+// stream, nothing waited for, nothing copied.  The product is a call whatever |x| is.
+int sella::hvp_device_apply(sella_hvp* o, const double* x, double* y) {
+    sella_calc* k = o->calc;
+    sella_ctx* c = k->c;
+    const long slot = o->calls;
+    const size_t ci = (size_t)(slot / HVP_CHUNK), r = (size_t)(slot % HVP_CHUNK), ld = (size_t)o->ld;
+    if (ci == o->chunks.size()) {
+        double* p;
+        SCHK(dev_alloc(c, o->chunk_bytes, &p));
+        o->chunks.push_back(p);
+        HIPCHK(s_memset0(c, p, o->chunk_bytes));
+    }
+    double* base = o->chunks[ci];
+    double *v = base + r * ld, *hv = base + (HVP_CHUNK + r) * ld;
+    int* flag = reinterpret_cast<int*>(base + (size_t)2 * HVP_CHUNK * ld) + r;
+    ++o->calls;
+    const int n = o->n;
+    SELLA_LAUNCHB(c, hvp_scatter_kernel, hvp_scatter_vb, 256, dim3(o->nb), dim3(256), 0, n, x, (const int*)o->inv, v, o->part);
+    if (k->kind == 1) return emt_hvp_state_apply(c, o->emt, v, hv, o->part, o->nb, o->inv, y, flag);
+    Mat* A = mat_get(c, k->A);
+    if (!A) {
+        set_error("hvp operator: the model calculator's matrix A is gone");
+        return SELLA_E_INVALID;
+    }
+    SCHK(launch_gemv_rows(c, A->d, n, n, A->ld, v, o->ld, 1, hv, o->ld, GemvEpi()));
+    if (k->nu > 0) SCHK(launch_gemv_rows(c, k->dconst, k->nu, n, o->ld, v, o->ld, 1, o->t, round_up(k->nu, 8), GemvEpi()));
+    SELLA_LAUNCHB(c, hvp_model_finish_kernel, hvp_model_finish_vb, 256, dim3(o->nb), dim3(256), 0, n, k->nu, o->ld,
+                  (const double*)o->S, (const double*)o->t, (const double*)o->part, o->nb, (const int*)o->inv, hv, y, flag);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
+int sella::hvp_dim(const sella_hvp* o) { return o->m; }
+sella_ctx* sella::hvp_ctx(const sella_hvp* o) { return o->calc->c; }
+
+// sella_matvec_fn: host vectors — upload, the device product, download, wait
+extern "C" int sella_hvp_matvec(void* user, const double* v, double* Av, int m) {
+    sella_hvp* o = static_cast<sella_hvp*>(user);
+    if (!o || !v || !Av || m != o->m) {
+        set_error("hvp operator: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    sella_ctx* c = o->calc->c;
+    SCHK(h2d_async(c, o->dx, v, (size_t)m * sizeof(double)));
+    SCHK(hvp_device_apply(o, o->dx, o->dy));
+    SCHK(d2h_async(c, Av, o->dy, (size_t)m * sizeof(double)));
+    return stream_wait(c);
+}
+
+// which products are recorded: the flags of the products since the last look, one wait
+static int hvp_sync_flags(sella_hvp* o) {
+    sella_ctx* c = o->calc->c;
+    const size_t have = o->flags.size(), want = (size_t)o->calls;
+    if (have == want) return SELLA_OK;
+    o->flags.resize(want);
+    for (size_t ci = have / HVP_CHUNK; ci * HVP_CHUNK < want; ++ci) {
+        const size_t lo = std::max(have, ci * HVP_CHUNK), hi = std::min(want, (ci + 1) * HVP_CHUNK);
+        const int* f = reinterpret_cast<const int*>(o->chunks[ci] + (size_t)2 * HVP_CHUNK * o->ld);
+        SCHK(d2h_async(c, o->flags.data() + lo, f + (lo - ci * HVP_CHUNK), (hi - lo) * sizeof(int)));
+    }
+    return stream_wait(c);
+}
+
+extern "C" int sella_hvp_npairs(sella_hvp* o) {
+    if (!o || hvp_sync_flags(o) != SELLA_OK) return 0;
+    int k = 0;
+    for (int f : o->flags) k += f != 0;
+    return k;
+}
+extern "C" long sella_hvp_calls(sella_hvp* o) { return o ? o->calls : 0; }
+
+// recorded pairs as (n x k) row-major matrices (columns = recorded products in call order), as sella_fd_pairs
+extern "C" int sella_hvp_pairs(sella_hvp* o, double* Vs, double* AVs) {
+    if (!o || !Vs || !AVs) return SELLA_E_INVALID;
+    SCHK(hvp_sync_flags(o));
+    sella_ctx* c = o->calc->c;
+    const int n = o->n;
+    const size_t ld = (size_t)o->ld;
+    int k = 0;
+    for (int f : o->flags) k += f != 0;
+    if (k == 0) return SELLA_OK;
+    std::vector<double> rows((size_t)2 * k * n);                       // recorded vectors, then their products, one per row
+    int p = 0;
+    for (size_t s = 0; s < o->flags.size(); ++s) {
+        if (!o->flags[s]) continue;
+        const double* base = o->chunks[s / HVP_CHUNK];
+        const size_t r = s % HVP_CHUNK;
+        SCHK(d2h_async(c, rows.data() + (size_t)p * n, base + r * ld, (size_t)n * sizeof(double)));
+        SCHK(d2h_async(c, rows.data() + (size_t)(k + p) * n, base + (HVP_CHUNK + r) * ld, (size_t)n * sizeof(double)));
+        ++p;
+    }
+    SCHK(stream_wait(c));
+    for (int q = 0; q < k; ++q)
+        for (int i = 0; i < n; ++i) {
+            Vs[(size_t)i * k + q] = rows[(size_t)q * n + i];
+            AVs[(size_t)i * k + q] = rows[(size_t)(k + q) * n + i];
+        }
+    return SELLA_OK;
+}
+
+extern "C" int sella_hvp_destroy(sella_hvp* o) {
+    if (o) hvp_release(o);
     return SELLA_OK;
 }

@@ -43,6 +43,7 @@ struct Dav {
     const Mat* A = nullptr;
     sella_matvec_fn matvec = nullptr;
     void* user = nullptr;
+    sella_hvp* hvp = nullptr;    // the analytic Hessian-vector operator (calc.hip): products stay on the device
     const Mat *Q = nullptr, *Qt = nullptr;
     const double* pevals_dev = nullptr;
     double pscale = 1.0;
@@ -144,11 +145,12 @@ int put_small(Dav& s, const double* h, int count, int stage, size_t dev_offset, 
     return SELLA_OK;
 }
 
-// y = A x on the device (dense) or through the host callback
+// y = A x on the device (dense, or the resident Hessian-vector operator) or through the host callback
 int apply_A(Dav& s, const double* x, double* y) {
     sella_ctx* c = s.c;
     s.nmatvec++;
     if (s.A) return launch_gemv_rows(c, s.A->d, s.n, s.n, s.A->ld, x, s.ld, 1, y, s.ld, GemvEpi());
+    if (s.hvp) return hvp_device_apply(s.hvp, x, y);    // queued behind whatever wrote x: nothing copied or waited for
     cohort_barrier(c, s.it, 2);               // (members of a cohort make the force calls behind their products together)
     s.hv.resize(s.n);
     s.hav.resize(s.n);
@@ -727,11 +729,12 @@ __global__ __launch_bounds__(256) void dav_rotate_columns_kernel(int n, int k, c
 
 using namespace sella;
 
-extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec, void* user,
-                              sella_mat hPvecs, sella_mat hPvecsT, const double* pevals, double pscale,
-                              int n, const double* v0, int nv0, double gamma, int method, int maxiter,
-                              const double* vref, double vreftol, double* lams_out, double* V_out,
-                              double* AV_out, int* k_out, int* nmatvec_out) {
+// sella_davidson and sella_davidson_hvp: one of hA, matvec, hvp is the operator
+static int davidson_run(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec, void* user, sella_hvp* hvp,
+                        sella_mat hPvecs, sella_mat hPvecsT, const double* pevals, double pscale,
+                        int n, const double* v0, int nv0, double gamma, int method, int maxiter,
+                        const double* vref, double vreftol, double* lams_out, double* V_out,
+                        double* AV_out, int* k_out, int* nmatvec_out) {
     if (!c || n <= 0 || !v0 || nv0 <= 0 || nv0 > n || !lams_out || !V_out || !AV_out || !k_out) {
         set_error("davidson: invalid arguments");
         return SELLA_E_INVALID;
@@ -756,12 +759,13 @@ extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec
         s.A = mat_get(c, hA);
         if (!s.A) return SELLA_E_INVALID;
         if (s.A->rows != n || s.A->cols != n) { set_error("davidson: A must be %d x %d", n, n); return SELLA_E_INVALID; }
-    } else if (!matvec) {
+    } else if (!matvec && !hvp) {
         set_error("davidson: neither a resident matrix nor a matvec callback was given");
         return SELLA_E_INVALID;
     }
     s.matvec = matvec;
     s.user = user;
+    s.hvp = hvp;
     s.pscale = pscale;
     if (hPvecs != SELLA_NO_MAT) {
         s.Q = mat_get(c, hPvecs);
@@ -1374,4 +1378,27 @@ extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec
     return SELLA_OK;
 #undef DCHK
 #undef DHIP
+}
+
+extern "C" int sella_davidson(sella_ctx* c, sella_mat hA, sella_matvec_fn matvec, void* user,
+                              sella_mat hPvecs, sella_mat hPvecsT, const double* pevals, double pscale,
+                              int n, const double* v0, int nv0, double gamma, int method, int maxiter,
+                              const double* vref, double vreftol, double* lams_out, double* V_out,
+                              double* AV_out, int* k_out, int* nmatvec_out) {
+    return davidson_run(c, hA, matvec, user, nullptr, hPvecs, hPvecsT, pevals, pscale, n, v0, nv0, gamma, method, maxiter, vref,
+                        vreftol, lams_out, V_out, AV_out, k_out, nmatvec_out);
+}
+
+// The same iteration over the analytic Hessian-vector operator of a calculator of the library (calc.hip, sella_hvp_*): the
+// third operator kind.  It stays on the synchronous iteration, like the callback operator.
+extern "C" int sella_davidson_hvp(sella_ctx* c, sella_hvp* op, sella_mat hPvecs, sella_mat hPvecsT, const double* pevals,
+                                  double pscale, int n, const double* v0, int nv0, double gamma, int method, int maxiter,
+                                  const double* vref, double vreftol, double* lams_out, double* V_out, double* AV_out,
+                                  int* k_out, int* nmatvec_out) {
+    if (!c || !op || hvp_ctx(op) != c || n != hvp_dim(op)) {
+        set_error("davidson: the Hessian-vector operator must belong to this context and have dimension n");
+        return SELLA_E_INVALID;
+    }
+    return davidson_run(c, SELLA_NO_MAT, nullptr, nullptr, op, hPvecs, hPvecsT, pevals, pscale, n, v0, nv0, gamma, method, maxiter,
+                        vref, vreftol, lams_out, V_out, AV_out, k_out, nmatvec_out);
 }

@@ -46,4 +46,19 @@ int emt_density_queue(sella_ctx* c, int n, const double* pos, const double* par,
                       const double* dconst, double rc, double acut, double cutoff, double beta, size_t extra_words,
                       EmtArgs* args, double** extra);
 
+// emt_hessian.hip: what the Hessian-vector operator (calc.hip, sella_hvp) keeps of a geometry — the argument block of the
+// density pass with its arrays, F2 and room for the n dots of a product, in ONE allocation of the state's own.
+struct EmtHvpState {
+    EmtArgs a;
+    double* F2 = nullptr;
+    double* cdot = nullptr;
+    double* own = nullptr;
+    size_t own_bytes = 0;
+};
+int emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                         const double* dconst, double rc, double acut, double cutoff, double beta, EmtHvpState* st);
+void emt_hvp_state_destroy(sella_ctx* c, EmtHvpState* st);
+int emt_hvp_state_apply(sella_ctx* c, const EmtHvpState& st, const double* v, double* hv, const double* part, int nb,
+                        const int* inv, double* y, int* flag);
+
 }  // namespace sella

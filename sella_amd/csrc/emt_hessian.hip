@@ -17,6 +17,9 @@
 //            diag(F2) G^T) -> H += G diag(F2) G^T on the matrix cores (launch_gemm) -> (H + H^T) / 2
 //   product: emt_f2 -> emt_hvp_dots (c_i = g_i . v) -> emt_hvp_gather ((H v)_i from c_i, c_j and the pair blocks), for up
 //            to HVP_KQ vectors per workgroup
+//   operator: the same two product kernels for ONE vector (emt_hvp1_dots, emt_hvp1_gather: 3 accumulators per thread instead
+//            of 24) on a state that is built once per geometry and owned by the operator (EmtHvpState: positions, sigma1,
+//            dEdsig, the lists, F2), device vector in, device vector out, nothing waited for (calc.hip, sella_hvp_*)
 // No atomics: an atom can be a neighbour through several images, and those visits belong to different threads unless
 // 256 divides N, so everything that lands in a shared place is added image by image with a barrier in between (one
 // writer per (i, j) within an image, images in index order); per-thread sums run in the order of the lists and are
@@ -37,6 +40,7 @@
 //   of gamma, atom i's share of B: 36 numbers, K_ab n_k n_l being symmetric in (a,b) and in (k,l)) -> emt_cell_embed (A +=
 //   (diag(F2) G^T)^T gamma) -> emt_cell_finish (B from the shares and gamma, summed in a fixed order; A^T into the last rows)
 #include <cmath>
+#include <type_traits>
 
 #include "emt.h"
 
@@ -202,16 +206,17 @@ struct EmtHvp {                             // k vectors: every array holds roun
     double* HV;                             // (k, 3n)
 };
 
-// c_i[q] = g_i . v_q = sum over the pairs of w' u . (v_j - v_i), vectors HVP_KQ vb.y .. of the product
-__device__ __forceinline__ void emt_hvp_dots_vb(const VB vb, EmtArgs a, EmtHvp o) {
+// c_i[q] = g_i . v_q = sum over the pairs of w' u . (v_j - v_i), vectors KQ vb.y .. of the product
+template <int KQ>
+__device__ __forceinline__ void emt_hvp_dots_body(const VB vb, const EmtArgs& a, const EmtHvp& o) {
     __shared__ double red[4];
     __shared__ int incomplete;
-    const int i = vb.x, q0 = vb.y * HVP_KQ;
+    const int i = vb.x, q0 = vb.y * KQ;
     const size_t n3 = (size_t)3 * a.n;
     const EmtAtom m = emt_atom(a, i);
-    double vi[HVP_KQ][3], acc[HVP_KQ];
+    double vi[KQ][3], acc[KQ];
 #pragma unroll
-    for (int q = 0; q < HVP_KQ; ++q) {
+    for (int q = 0; q < KQ; ++q) {
         const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * i;
         vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
         acc[q] = 0.0;
@@ -220,32 +225,37 @@ __device__ __forceinline__ void emt_hvp_dots_vb(const VB vb, EmtArgs a, EmtHvp o
         EmtPair p;
         if (!emt_pair(a, m, t, p)) return;
 #pragma unroll
-        for (int q = 0; q < HVP_KQ; ++q) {
+        for (int q = 0; q < KQ; ++q) {
             const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * p.j;
             acc[q] += p.wp_ij * (p.ux * (v[0] - vi[q][0]) + p.uy * (v[1] - vi[q][1]) + p.uz * (v[2] - vi[q][2]));
         }
     };
     emt_by_image<false>(a, i, &incomplete, visit);
 #pragma unroll
-    for (int q = 0; q < HVP_KQ; ++q) {
+    for (int q = 0; q < KQ; ++q) {
         const double s = block_sum(acc[q], red);
         if (threadIdx.x == 0) o.cdot[(size_t)(q0 + q) * a.n + i] = s;
     }
 }
+__device__ __forceinline__ void emt_hvp_dots_vb(const VB vb, EmtArgs a, EmtHvp o) { emt_hvp_dots_body<HVP_KQ>(vb, a, o); }
 __global__ __launch_bounds__(256) void emt_hvp_dots_kernel(EmtArgs a, EmtHvp o) { emt_hvp_dots_vb(vb_hw(), a, o); }
+__device__ __forceinline__ void emt_hvp1_dots_vb(const VB vb, EmtArgs a, EmtHvp o) { emt_hvp_dots_body<1>(vb, a, o); }
+__global__ __launch_bounds__(256) void emt_hvp1_dots_kernel(EmtArgs a, EmtHvp o) { emt_hvp1_dots_vb(vb_hw(), a, o); }
 
 // (H v)_i = sum over the pairs of  -u (F2_i c_i w'_ij + F2_j c_j w'_ji)  +  K (v_i - v_j):
 // g_i on atom i is -sum w'_ij u, g_j on atom i is -w'_ji u (atom i seen from j lies along -u)
-__device__ __forceinline__ void emt_hvp_gather_vb(const VB vb, EmtArgs a, EmtHvp o) {
+// store(q, sx, sy, sz), on thread 0: where the three components of vector q0 + q go
+template <int KQ, class Store>
+__device__ __forceinline__ void emt_hvp_gather_body(const VB vb, const EmtArgs& a, const EmtHvp& o, Store store) {
     __shared__ double red[4];
     __shared__ int incomplete;
-    const int i = vb.x, q0 = vb.y * HVP_KQ;
+    const int i = vb.x, q0 = vb.y * KQ;
     const size_t n3 = (size_t)3 * a.n;
     const EmtAtom m = emt_atom(a, i);
     const double f2i = o.F2[i];
-    double vi[HVP_KQ][3], fc[HVP_KQ], acc[HVP_KQ][3];
+    double vi[KQ][3], fc[KQ], acc[KQ][3];
 #pragma unroll
-    for (int q = 0; q < HVP_KQ; ++q) {
+    for (int q = 0; q < KQ; ++q) {
         const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * i;
         vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
         fc[q] = f2i * o.cdot[(size_t)(q0 + q) * a.n + i];
@@ -257,7 +267,7 @@ __device__ __forceinline__ void emt_hvp_gather_vb(const VB vb, EmtArgs a, EmtHvp
         const double c1 = p.e1 / p.r, c2 = p.e2 - c1;
         const double f2j = o.F2[p.j];
 #pragma unroll
-        for (int q = 0; q < HVP_KQ; ++q) {
+        for (int q = 0; q < KQ; ++q) {
             const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * p.j;
             const double dx = vi[q][0] - v[0], dy = vi[q][1] - v[1], dz = vi[q][2] - v[2];
             const double along = c2 * (p.ux * dx + p.uy * dy + p.uz * dz)
@@ -269,15 +279,49 @@ __device__ __forceinline__ void emt_hvp_gather_vb(const VB vb, EmtArgs a, EmtHvp
     };
     emt_by_image<false>(a, i, &incomplete, visit);
 #pragma unroll
-    for (int q = 0; q < HVP_KQ; ++q) {
+    for (int q = 0; q < KQ; ++q) {
         const double sx = block_sum(acc[q][0], red), sy = block_sum(acc[q][1], red), sz = block_sum(acc[q][2], red);
-        if (threadIdx.x == 0) {
-            double* out = o.HV + (size_t)(q0 + q) * n3 + 3 * i;
-            out[0] = sx; out[1] = sy; out[2] = sz;
-        }
+        if (threadIdx.x == 0) store(q, sx, sy, sz);
     }
 }
+__device__ __forceinline__ void emt_hvp_gather_vb(const VB vb, EmtArgs a, EmtHvp o) {
+    const size_t n3 = (size_t)3 * a.n;
+    emt_hvp_gather_body<HVP_KQ>(vb, a, o, [&](int q, double sx, double sy, double sz) {
+        double* out = o.HV + (size_t)(vb.y * HVP_KQ + q) * n3 + 3 * vb.x;
+        out[0] = sx; out[1] = sy; out[2] = sz;
+    });
+}
 __global__ __launch_bounds__(256) void emt_hvp_gather_kernel(EmtArgs a, EmtHvp o) { emt_hvp_gather_vb(vb_hw(), a, o); }
+
+// One vector of the operator (calc.hip, sella_hvp): V and HV of `o` are rows of its pair record (full length 3n).  |v|^2
+// comes in `nb` partial sums; a vanishing vector (|v| < 1e-12) gives a zero product and flag 0, as sella_fd_matvec does.
+// The rows of the free coordinates also go into the eigensolver's vector y (inv: full coordinate -> its index there, -1
+// if pinned; null: all free).
+struct EmtHvpOut1 {
+    const double* part; int nb;
+    const int* inv;
+    double* y;
+    int* flag;
+};
+__device__ __forceinline__ void emt_hvp1_gather_vb(const VB vb, EmtArgs a, EmtHvp o, EmtHvpOut1 w) {
+    __shared__ double red1[4];
+    double s = 0.0;
+    for (int b = threadIdx.x; b < w.nb; b += 256) s += w.part[b];
+    s = block_sum(s, red1);
+    const bool live = !(sqrt(s) < 1e-12);
+    if (vb.x == 0 && threadIdx.x == 0) *w.flag = live ? 1 : 0;
+    emt_hvp_gather_body<1>(vb, a, o, [&](int, double sx, double sy, double sz) {
+        const int p = 3 * vb.x;
+        const double h[3] = {live ? sx : 0.0, live ? sy : 0.0, live ? sz : 0.0};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            o.HV[p + k] = h[k];
+            const int q = w.inv ? w.inv[p + k] : p + k;
+            if (q >= 0) w.y[q] = h[k];
+        }
+    });
+}
+__global__ __launch_bounds__(256) void emt_hvp1_gather_kernel(EmtArgs a, EmtHvp o, EmtHvpOut1 w) { emt_hvp1_gather_vb(vb_hw(), a, o, w); }
 
 // ---- the cell columns ---------------------------------------------------------------------------------------------------
 // symmetric index of (a, b), a, b in 0..2, in the order xx, yy, zz, yz, xz, xy
@@ -571,6 +615,56 @@ int sella::emt_hvp_resident(sella_ctx* c, int n, const double* pos, const double
     HIPCHK(hipGetLastError());
     SCHK(d2h_async(c, HV, o.HV, (size_t)k * n3 * sizeof(double)));
     return stream_wait(c);
+}
+
+// ---- the resident state of the Hessian-vector operator (emt.h) ---------------------------------------------------------
+// One density pass and one emt_f2 at `pos`; what they leave in scratch slot SCR_MISC0 (positions, sigma1, dEdsig, the
+// lists, F2 — and the parameter table and shifts unless `dconst` holds them) is copied into an allocation of the state's
+// own, because the next force call reuses the slot.
+int sella::emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                                const double* dconst, double rc, double acut, double cutoff, double beta, EmtHvpState* st) {
+    EmtArgs a;
+    double* ex;                                                       // F2 (n), c_i = g_i . v (n)
+    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, (size_t)2 * n, &a, &ex));
+    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, ex);
+    HIPCHK(hipGetLastError());
+    const char* lo = reinterpret_cast<const char*>(a.pos);            // (the positions lead the slot)
+    const char* hi = reinterpret_cast<const char*>(ex + (size_t)2 * n);
+    st->own_bytes = (size_t)(hi - lo);
+    SCHK(dev_alloc(c, st->own_bytes, &st->own));
+    HIPCHK(s_memcpy(c, st->own, lo, st->own_bytes, hipMemcpyDeviceToDevice));
+    char* base = reinterpret_cast<char*>(st->own);
+    auto moved = [&](auto*& p) {                                      // pointers into the slot follow the copy
+        const char* q = reinterpret_cast<const char*>(p);
+        if (q >= lo && q < hi) p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(base + (q - lo));
+    };
+    moved(a.pos); moved(a.shifts); moved(a.sigma1); moved(a.epair); moved(a.dEdsig); moved(a.eatom); moved(a.grad); moved(a.nbr);
+    moved(a.p.E0); moved(a.p.s0); moved(a.p.V0); moved(a.p.eta2); moved(a.p.kappa); moved(a.p.lam); moved(a.p.n0);
+    moved(a.p.gamma1); moved(a.p.gamma2);
+    moved(ex);
+    st->a = a;
+    st->F2 = ex;
+    st->cdot = ex + n;
+    return stream_wait(c);
+}
+
+void sella::emt_hvp_state_destroy(sella_ctx* c, EmtHvpState* st) {
+    if (st->own) dev_free(c, st->own, st->own_bytes);
+    st->own = nullptr;
+}
+
+// hv = H v (rows of 3n on the device) and the free rows into y: two launches on the context's stream, nothing waited for
+int sella::emt_hvp_state_apply(sella_ctx* c, const EmtHvpState& st, const double* v, double* hv, const double* part, int nb,
+                               const int* inv, double* y, int* flag) {
+    EmtHvp o;
+    o.F2 = st.F2; o.V = v; o.cdot = st.cdot; o.HV = hv;
+    EmtHvpOut1 w;
+    w.part = part; w.nb = nb; w.inv = inv; w.y = y; w.flag = flag;
+    const dim3 grid(st.a.n);
+    SELLA_LAUNCHB(c, emt_hvp1_dots_kernel, emt_hvp1_dots_vb, 256, grid, dim3(256), 0, st.a, o);
+    SELLA_LAUNCHB(c, emt_hvp1_gather_kernel, emt_hvp1_gather_vb, 256, grid, dim3(256), 0, st.a, o, w);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
 }
 
 extern "C" int sella_emt_hessian(sella_ctx* c, int n, const double* pos, const double* par /* 9 x n */, int nshift,

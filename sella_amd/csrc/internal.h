@@ -392,6 +392,11 @@ int emt_hvp_resident(sella_ctx* c, int n, const double* pos, const double* par, 
 // *aux_dev / *naux = what the energy is assembled from.  calc_finish: energy from the read-back aux values, after the wait.
 int calc_queue(sella_calc* k, const double* x, double** g_dev, double** aux_dev, int* naux);
 double calc_finish(sella_calc* k, const double* x, const double* aux_host);
+// the analytic Hessian-vector operator (calc.hip, sella_hvp_*) as sella_davidson_hvp sees it: y = (H vfull)[free] for device
+// vectors of hvp_dim() entries, queued on the stream of hvp_ctx(), nothing waited for
+int hvp_device_apply(sella_hvp* op, const double* x, double* y);
+int hvp_dim(const sella_hvp* op);
+sella_ctx* hvp_ctx(const sella_hvp* op);
 // stepper.hip: step family on m modes = rows idx[0..m) of a device panel (gathered into matrices the stepper owns)
 int stepper_from_panel(sella_ctx* c, int kind, const double* src, int ld, const int* idx, int m, int n, const double* ev,
                        const double* gh, int order, sella_stepper** out);

@@ -313,6 +313,12 @@ class Context:
         elif isinstance(A, DeviceFdOperator):
             # the finite-difference Hessian of a calculator that lives in the library: its products are library calls
             hA, cb, user = SELLA_NO_MAT, A.callback(), A._h
+        elif isinstance(A, DeviceHvpOperator):
+            # the analytic Hessian-vector operator of such a calculator: the products never leave the device (unless it
+            # asks to be the host callback of the unchanged solver, `through_host`)
+            hA, cb = SELLA_NO_MAT, None
+            if A.through_host:
+                cb, user = A.callback(), A._h
         else:
             hA = SELLA_NO_MAT
 
@@ -328,13 +334,15 @@ class Context:
             cb = _lib.MATVEC_FN(_cb)
         pe = as_f64(pevals) if pevals is not None else None
         vr = as_f64(vref) if vref is not None else None
-        st = _lib.lib().sella_davidson(
-            self._h, hA, cb, user,
-            SELLA_NO_MAT if Pvecs is None else Pvecs.handle,
-            SELLA_NO_MAT if PvecsT is None else PvecsT.handle,
-            ptr(pe), float(pscale), int(n), ptr(v0), nv0, float(gamma),
-            DAVIDSON_METHODS[method], int(maxiter), ptr(vr), float(vreftol),
-            ptr(lams), ptr(V), ptr(AV), byref(k), byref(nmv))
+        tail = (SELLA_NO_MAT if Pvecs is None else Pvecs.handle,
+                SELLA_NO_MAT if PvecsT is None else PvecsT.handle,
+                ptr(pe), float(pscale), int(n), ptr(v0), nv0, float(gamma),
+                DAVIDSON_METHODS[method], int(maxiter), ptr(vr), float(vreftol),
+                ptr(lams), ptr(V), ptr(AV), byref(k), byref(nmv))
+        if cb is None:
+            st = _lib.lib().sella_davidson_hvp(self._h, A._h, *tail)
+        else:
+            st = _lib.lib().sella_davidson(self._h, hA, cb, user, *tail)
         if err:
             raise err[0]
         check(st)
@@ -773,6 +781,56 @@ class DeviceFdOperator:
         Vs, AVs = np.empty((self.ntrue, k)), np.empty((self.ntrue, k))
         if k:
             check(_lib.lib().sella_fd_pairs(self._h, ptr(Vs), ptr(AVs)))
+        return Vs, AVs
+
+    Vs = property(lambda self: self._pairs()[0])
+    AVs = property(lambda self: self._pairs()[1])
+
+
+class DeviceHvpOperator:
+    """The analytic Hessian of a `DeviceCalculator` at x0 as a matrix-free operator (`sella_hvp_*`): what depends on the
+    geometry is built once and stays on the device, a product is exact and is not a force call.  `free`: the coordinates
+    the eigensolver sees (ascending; None: all).  Passed to `Context.davidson` as the operator (`sella_davidson_hvp`: the
+    products stay on the device); `apply(v)` is one product with host vectors; `Vs` / `AVs` afterwards hold the recorded
+    pairs (full space, one column per product of a non-vanishing vector), like `DeviceFdOperator`.  `through_host=True`
+    makes `Context.davidson` run the unchanged `sella_davidson` with `sella_hvp_matvec` as its host callback instead (same
+    results; for comparisons and measurements)."""
+
+    def __init__(self, calc, x0, free=None, through_host=False):
+        self.through_host = bool(through_host)
+        x0 = as_f64(x0).ravel()
+        self.calc, self.ntrue = calc, x0.size
+        self._free = None if free is None else np.ascontiguousarray(free, dtype=np.int32)
+        n = self.ntrue if self._free is None else len(self._free)
+        self.shape = (n, n)
+        h = c_void_p()
+        check(_lib.lib().sella_hvp_create(calc._h, self.ntrue, ptr(x0),
+                                          None if self._free is None else self._free.ctypes.data_as(c_void_p),
+                                          0 if self._free is None else len(self._free), byref(h)))
+        self._h = h
+        self._fin = calc.ctx.child(weakref.finalize(self, _lib.lib().sella_hvp_destroy, h))
+
+    def callback(self):
+        """`sella_hvp_matvec` as the `sella_matvec_fn` of the unchanged `sella_davidson` (host vectors per product)."""
+        return ctypes.cast(_lib.lib().sella_hvp_matvec, _lib.MATVEC_FN)
+
+    def apply(self, v):
+        """(H vfull)[free] for the free entries v of vfull: one product through `sella_hvp_matvec`."""
+        v = np.ascontiguousarray(as_f64(v).ravel())
+        if v.size != self.shape[0]:
+            raise ValueError(f'expected a vector of length {self.shape[0]}, got {v.size}')
+        out = np.empty_like(v)
+        check(_lib.lib().sella_hvp_matvec(self._h, ptr(v), ptr(out), v.size))
+        return out
+
+    dot = apply
+    calls = property(lambda self: int(_lib.lib().sella_hvp_calls(self._h)))
+
+    def _pairs(self):
+        k = int(_lib.lib().sella_hvp_npairs(self._h))
+        Vs, AVs = np.empty((self.ntrue, k)), np.empty((self.ntrue, k))
+        if k:
+            check(_lib.lib().sella_hvp_pairs(self._h, ptr(Vs), ptr(AVs)))
         return Vs, AVs
 
     Vs = property(lambda self: self._pairs()[0])

@@ -3,6 +3,8 @@
   NumericalHessian   finite-difference Hessian-vector products through the calculator
                      boundary (linalg.py:14-101); the projection products U v / U^T Av run on
                      the device when the basis is large.
+  AnalyticHessian    the same operator with exact products from a calculator's own Hessian-vector product (no
+                     counterpart in the reference)
   MatrixSum          operator sum (linalg.py:104-140)
   ApproximateHessian owner of the n x n approximate Hessian B (linalg.py:143-353).  B lives in
                      HBM (`_B_gpu`); its eigenvectors stay on the device both as columns and as
@@ -99,6 +101,46 @@ class NumericalHessian(LinearOperator):
             Av = scale * (ahead - self.g0) / self.eta
         self._pairs.append((v.copy(), Av))
         return self._restrict(Av)
+
+    def __add__(self, other):
+        return MatrixSum(self, other)
+
+    def _transpose(self):
+        return self
+
+
+class AnalyticHessian(LinearOperator):
+    """H v in closed form, `hvp(V (k, ntrue)) -> H V[q] (k, ntrue)`, optionally seen through a basis Ufree (ntrue x n):
+    v -> Ufree^T H Ufree v.  The host-level counterpart of `NumericalHessian` for what the device operator
+    (`DeviceHvpOperator`) does not cover: a foreign calculator or a user's callable, a basis that is no selection of
+    coordinates, curved constraints.  Every product of a non-vanishing vector is remembered in `Vs` / `AVs` (full space, one
+    column each) for the secant pairs of `PES.diag`; a vector with |v| < 1e-12 gives zero, counts as a call and is not."""
+    dtype = np.dtype('float64')
+
+    def __init__(self, hvp, n, Ufree=None):
+        self.hvp, self.ntrue, self.Uproj = hvp, int(n), Ufree
+        self.calls = 0
+        if Ufree is not None and Ufree.shape[0] != self.ntrue:
+            raise ValueError('Ufree must have %d rows' % self.ntrue)
+        self._U_identity = Ufree is None or is_identity(Ufree)
+        m = self.ntrue if Ufree is None else Ufree.shape[1]
+        super().__init__(self.dtype, (m, m))
+        self._pairs = []
+
+    _stacked = NumericalHessian._stacked
+    Vs = property(lambda self: self._stacked(0))
+    AVs = property(lambda self: self._stacked(1))
+
+    def _matvec(self, v):
+        self.calls += 1
+        v = np.asarray(v, dtype=np.float64).ravel()
+        if not self._U_identity:
+            v = self.Uproj @ v
+        if np.linalg.norm(v) < 1e-12:
+            return np.zeros(self.shape[0])
+        Av = np.asarray(self.hvp(v.reshape(1, -1)), dtype=np.float64).reshape(self.ntrue)
+        self._pairs.append((v.copy(), Av))
+        return Av if self._U_identity else self.Uproj.T @ Av
 
     def __add__(self, other):
         return MatrixSum(self, other)

@@ -46,10 +46,23 @@ class Sella(Optimizer):
                  append_trajectory=False, rs=None, nsteps_per_diag=3, diag_every_n=None,
                  hessian_function=None, optimize_cell=False, cell_mask=None, exp_cell_factor=None,
                  scalar_pressure=0.0, smax=None, allow_fragments=False, niggli=False,
-                 refine_initial_hessian=False, save_hessian=None, exact_geodesic=None, **kwargs):
+                 refine_initial_hessian=False, save_hessian=None, exact_geodesic=None, hessian_vector_product=None,
+                 **kwargs):
         # keyword set of the reference constructor (optimize.py:42-80).  The cell keywords (cell_mask,
         # exp_cell_factor, scalar_pressure, smax, niggli, refine_initial_hessian, save_hessian) only act with
         # optimize_cell=True, there as here.
+        # hessian_vector_product (True: the calculator's own; or f(atoms, V (k, 3N)) -> (k, 3N)): the iterative
+        # diagonalisation takes exact products instead of finite differences of the gradient (no counterpart in the
+        # reference); Cartesian coordinates at fixed cell only
+        if hessian_vector_product is False:
+            hessian_vector_product = None
+        if hessian_vector_product is not None:
+            if hessian_function is not None:
+                raise ValueError('hessian_function and hessian_vector_product are two sources of curvature: give one')
+            if internal or optimize_cell:
+                raise NotImplementedError('hessian_vector_product is implemented for Cartesian coordinates at fixed cell only '
+                                          '(not with internal=True or optimize_cell=True)')
+            kwargs = dict(kwargs, hessian_vector_product=hessian_vector_product)
         if optimize_cell:
             self._check_cell_run(atoms, order, internal, niggli)
         self.optimize_cell = bool(optimize_cell)

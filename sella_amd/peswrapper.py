@@ -20,7 +20,7 @@ from .device import get_context
 from .eigensolvers import rayleigh_ritz
 from .hessian_update import symmetrize_Y
 from .internal import Constraints, DuplicateInternalError
-from .linalg import ApproximateHessian, NumericalHessian
+from .linalg import AnalyticHessian, ApproximateHessian, NumericalHessian
 from .utilities.math import register_selection, selection_of, is_identity, shared_identity
 
 
@@ -104,10 +104,15 @@ def open_trajectory(name, atoms, append=False):
 
 class PES:
     n_cell_dof = 0
+    # `hessian_vector_product=`: exact products for the iterative diagonalisation, Cartesian coordinates only (the
+    # subclasses for internal coordinates and for the cell refuse the keyword)
+    _accepts_hvp = True
 
     def __init__(self, atoms, H0=None, constraints=None, eigensolver='jd0', trajectory=None,
-                 eta=1e-4, v0=None, proj_trans=None, proj_rot=None, hessian_function=None):
+                 eta=1e-4, v0=None, proj_trans=None, proj_rot=None, hessian_function=None, hessian_vector_product=None):
         self.atoms = atoms
+        self._hvp, self._hvp_from_calc = self._resolve_hvp(atoms, hessian_vector_product), hessian_vector_product is True
+        self.nhvp = 0                                        # Hessian-vector products taken (`neval` counts force calls only)
         self.cons = self._constraint_set(atoms, constraints, proj_trans, proj_rot)
         self.eigensolver, self.eta, self.v0 = eigensolver, eta, v0
         self.hessian_function = hessian_function
@@ -123,6 +128,26 @@ class PES:
         self.first_diag = True
         self._basis_cache = _LRU2()
         self.set_H(H0, initialized=H0 is not None)
+
+    def _resolve_hvp(self, atoms, hvp):
+        """`V (k, 3N) -> H V[q] (k, 3N)` at the geometry the atoms have when it is called, from the keyword
+        `hessian_vector_product`: True takes the calculator's own, a callable f(atoms, V) is taken as it is."""
+        if hvp is None or hvp is False:
+            return None
+        if not self._accepts_hvp:
+            raise NotImplementedError(f'hessian_vector_product is not implemented for {type(self).__name__}: the products '
+                                      f'exist in Cartesian coordinates at fixed cell only')
+        if hvp is True:
+            from .atoms import supports_hessian
+            calc = getattr(atoms, 'calc', None)
+            own = getattr(calc, 'hessian_vector_product', None)
+            if not supports_hessian(calc) or not callable(own):
+                raise NotImplementedError(f'hessian_vector_product=True needs a calculator with its own Hessian-vector '
+                                          f'product, and {type(calc).__name__} has none')
+            return lambda V: own(self.atoms, V)
+        if not callable(hvp):
+            raise TypeError('hessian_vector_product must be True or a callable f(atoms, V (k, 3N)) -> (k, 3N)')
+        return lambda V: hvp(self.atoms, V)
 
     @staticmethod
     def _constraint_set(atoms, constraints, proj_trans, proj_rot):
@@ -402,9 +427,15 @@ class PES:
                 v0 = g if is_identity(Ufree) else g @ Ufree
             if np.linalg.norm(v0) < 1e-12:
                 v0 = None
-        Hproj = self._library_fd_operator(Ufree, threepoint)
-        if Hproj is None:
-            Hproj = NumericalHessian(self._calc_eg, self.get_x(), self.get_g(), self.eta, threepoint, Ufree)
+        if self._hvp is not None:
+            # exact products (`hessian_vector_product=`): no displacement, so `threepoint` has no meaning here
+            Hproj = self._library_hvp_operator(Ufree)
+            if Hproj is None:
+                Hproj = AnalyticHessian(self._hvp, self.ncart, Ufree)
+        else:
+            Hproj = self._library_fd_operator(Ufree, threepoint)
+            if Hproj is None:
+                Hproj = NumericalHessian(self._calc_eg, self.get_x(), self.get_g(), self.eta, threepoint, Ufree)
         A = Hproj
         Hc = None
         if self._has_curved_constraints():
@@ -415,7 +446,9 @@ class PES:
         rayleigh_ritz(A, gamma, None if P_is_none else P, v0=v0, method=self.eigensolver, maxiter=maxiter)
 
         Vs, AVs = Hproj.Vs, Hproj.AVs
-        if not isinstance(Hproj, NumericalHessian):
+        if self._hvp is not None:
+            self.nhvp += Hproj.calls                                 # products, not force calls
+        elif not isinstance(Hproj, NumericalHessian):
             self.neval += Hproj.calls * (2 if threepoint else 1)     # force calls the library made itself
         # Ritz vectors of the collected full-space iterates (peswrapper.py:545-551)
         Atilde = Vs.T @ symmetrize_Y(Vs, AVs, symm=2)
@@ -430,7 +463,15 @@ class PES:
         library (`atoms.calc.device_calculator()`): the force calls of the Davidson run are then library calls, with no
         interpreter frame between them.  Needs a basis that is the identity or a selection of coordinates, no curved
         constraints, and nobody listening per force call (a trajectory writes one image per call, peswrapper.py:409-418)."""
-        from .utilities.math import selection_of
+        route = self._library_route(Ufree)
+        if route is None:
+            return None
+        from .device import DeviceFdOperator
+        return DeviceFdOperator(route[0], self.get_x(), self.get_g(), self.eta, threepoint, route[1])
+
+    def _library_route(self, Ufree):
+        """(the calculator's library form, free coordinates or None for all) when an operator of the library can stand
+        for the Hessian seen through Ufree, else None (the conditions in `_library_fd_operator`)."""
         calc = getattr(self.atoms, 'calc', None)
         maker = getattr(calc, 'device_calculator', None)
         if maker is None or self.traj is not None or self._has_curved_constraints() or type(self) is not PES:
@@ -445,8 +486,19 @@ class PES:
         dc = maker()
         if dc is None:
             return None
-        from .device import DeviceFdOperator
-        return DeviceFdOperator(dc, self.get_x(), self.get_g(), self.eta, threepoint, free)
+        return dc, free
+
+    def _library_hvp_operator(self, Ufree):
+        """The analytic Hessian as a library object (`sella_hvp_*`, `DeviceHvpOperator`) under the conditions of
+        `_library_fd_operator`, when the products are the calculator's own (`hessian_vector_product=True`): its state at
+        this geometry is built once, and the products of the Davidson run never leave the device."""
+        if not self._hvp_from_calc:
+            return None
+        route = self._library_route(Ufree)
+        if route is None:
+            return None
+        from .device import DeviceHvpOperator
+        return DeviceHvpOperator(route[0], self.get_x(), route[1])
 
     def get_projected_forces(self):
         g = self.get_g()
@@ -702,6 +754,8 @@ class _BFactor:
 
 
 class InternalPES(PES):
+    _accepts_hvp = False
+
     def __init__(self, atoms, internals, *args, H0=None, iterative_stepper=0, auto_find_internals=True,
                  exact_geodesic=False, **kwargs):
         if internals is None or internals is True:
@@ -1127,10 +1181,13 @@ class CellCartesianPES(PES):
     hessian_function(atoms) returns the (3N + 9)-square Hessian in the coordinates [positions; cell.ravel()] (lattice
     vectors in the rows of the cell, positions fixed while the cell varies), as an array or a `DeviceMatrix`, e.g.
     `EMT.get_device_cell_hessian`; `calculate_hessian` carries it into the PES's own coordinates."""
+    _accepts_hvp = False
 
     def __init__(self, atoms, H0=None, constraints=None, eigensolver='jd0', trajectory=None, eta=1e-4, v0=None,
                  proj_trans=None, proj_rot=None, hessian_function=None, exp_cell_factor=None, cell_mask=None,
-                 scalar_pressure=0.0, refine_initial_hessian=False, hessian_delta=1e-5, save_hessian=None):
+                 scalar_pressure=0.0, refine_initial_hessian=False, hessian_delta=1e-5, save_hessian=None,
+                 hessian_vector_product=None):
+        self._resolve_hvp(atoms, hessian_vector_product)            # (refused: no products in the cell coordinates)
         self.orig_cell = np.array(atoms.get_cell(), dtype=np.float64)
         self.exp_cell_factor = float(len(atoms)) if exp_cell_factor is None else float(exp_cell_factor)
         mask = np.ones((3, 3), dtype=bool) if cell_mask is None else np.asarray(cell_mask, dtype=bool).reshape((3, 3))
