@@ -550,6 +550,22 @@ int sella_fd_destroy(sella_fd* fd);
  * Every product of a non-vanishing vector is remembered, vfull and H vfull in full length (pinned rows included), on the
  * device in chunks that are added as products arrive; sella_hvp_pairs returns them like sella_fd_pairs, (n x k) row-major,
  * k = sella_hvp_npairs.  |v| < 1e-12 gives a zero product, counts as a call (sella_hvp_calls) and is not recorded.
+ * Block products — up to 16 vectors, the rows of a panel, through the batched kernels on the same resident state (emt: the
+ * pair geometry of a visit is evaluated once for all rows; model: A and the rows u_j streamed once on the matrix cores):
+ *   sella_hvp_apply_block      HV (k x m, host) = the products of the rows of V (k x m, host), any k >= 1, in chunks of 16.
+ *   sella_davidson_block_hvp   sella_davidson_block (above: the block method, its preconditioners, start block, stopping
+ *                        rule |r| <= tol |theta|, thick restarts and outputs; no counterpart in the reference, whose
+ *                        rayleigh_ritz adds one vector per iteration, sella/eigensolvers.py:111-112; converged pairs equal
+ *                        those of exact(), sella/eigensolvers.py:9-28) with this operator in place of the resident matrix:
+ *                        the lowest eigenpairs without n x n storage.  Arguments from Pvecs on as sella_davidson_block's,
+ *                        n is the operator's m, one rank (no gather); the panels are round_up(m, 8) apart.  *nmatvec counts
+ *                        every row the operator was applied to (= the growth of sella_hvp_calls).  SELLA_E_INVALID: a null
+ *                        or foreign op, nev <= 0, nev > m, block < 1 or > 16, nv0 > 16, Pvecs / PvecsT not m x m.  The
+ *                        operator must outlive the call; the re-entrancy contract above applies.
+ *   sella_hvp_diag       diag(H)[idx] (m, host) at the operator's geometry — the diagonal preconditioner of the block method.
+ *                        Neither a force call nor a product (sella_hvp_calls unchanged).
+ * A block product is nh calls, is NOT entered in the pair record (the record feeds the secant update of PES.diag) and has no
+ * vanishing-vector rule: a zero row gives a zero row.
  * The operator must be destroyed before its calculator and context.  SELLA_E_INVALID: a null pointer, n != sella_calc_dim,
  * m <= 0 or m > n with idx given, idx not ascending, an m (sella_hvp_matvec) / n (sella_davidson_hvp) that is not the
  * operator's.                                                                                                            */
@@ -565,6 +581,12 @@ int sella_davidson_hvp(sella_ctx* ctx, sella_hvp* op,
                        int n, const double* v0, int nv0, double gamma, int method, int maxiter,
                        const double* vref, double vreftol,
                        double* lams, double* V, double* AV, int* k, int* nmatvec);
+int sella_hvp_apply_block(sella_hvp* op, const double* V, int k, double* HV);
+int sella_hvp_diag(sella_hvp* op, double* diag);
+int sella_davidson_block_hvp(sella_ctx* ctx, sella_hvp* op, sella_mat Pvecs, sella_mat PvecsT,
+                             const double* pevals, const double* diag, const double* V0, int nv0, int nev,
+                             int block, int maxvec, double tol, int maxiter, double* lams, double* V,
+                             double* res, int* niter, int* nmatvec, int* nconv);
 
 /* ---- a whole search in the library --------------------------------------------------------------------------- */
 /* `Sella(atoms, ...).run(fmax, steps)` (sella/optimize/optimize.py:42-440 under ASE's Optimizer.irun) for the

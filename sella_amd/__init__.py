@@ -21,6 +21,7 @@ _LAZY = {
     'Atoms': ('sella_amd.atoms', 'Atoms'),
     'LibrarySearch': ('sella_amd.search', 'LibrarySearch'),
     'EnsembleThreads': ('sella_amd.ensemble', 'EnsembleThreads'),
+    'lowest_modes': ('sella_amd.eigensolvers', 'lowest_modes'),
 }
 
 

@@ -137,6 +137,10 @@ SIGNATURES = {
     'sella_davidson_hvp': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p,
                                    c_double, c_int, c_void_p, c_int, c_double, c_int, c_int, c_void_p,
                                    c_double, c_void_p, c_void_p, c_void_p, c_int_p, c_int_p]),
+    'sella_hvp_apply_block': (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
+    'sella_hvp_diag': (c_int, [c_void_p, c_void_p]),
+    'sella_davidson_block_hvp': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                         c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_int_p, c_int_p, c_int_p]),
     'sella_search_create': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(SearchParams),
                                     POINTER(c_void_p)]),
     'sella_search_seed': (c_int, [c_void_p, c_double, c_void_p]),

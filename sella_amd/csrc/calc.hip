@@ -11,7 +11,8 @@
 //   sella_hvp_*          H v in closed form (EMT: emt_hessian.hip; model: A v + sum_j 2 c (u_j . x0)(u_j . v) u_j) through the
 //                        same selection, on a state built once at x0 and owned by the operator: device vector in, device
 //                        vector out, no host wait per product (the third operator kind of sella_davidson, davidson.hip);
-//                        the pairs are recorded on the device.  Not force calls.
+//                        the pairs are recorded on the device.  Not force calls.  The same for the rows of a device panel
+//                        (hvp_device_apply_block: the operator of sella_davidson_block_hvp; not recorded), and diag(H)
 #include "emt.h"
 
 #include <algorithm>
@@ -106,6 +107,60 @@ __global__ __launch_bounds__(256) void hvp_model_finish_kernel(int n, int nu, in
                                                                const double* __restrict__ t, const double* __restrict__ part, int nb,
                                                                const int* __restrict__ inv, double* __restrict__ hv, double* __restrict__ y,
                                                                int* __restrict__ flag) { hvp_model_finish_vb(vb_hw(), n, nu, ld, S, t, part, nb, inv, hv, y, flag); }
+
+// The block form of hvp_scatter: the nh <= 16 rows of the eigensolver's panel X (row h at X + h ldx) as full-length rows,
+// zero on the pinned coordinates and in the rows from nh on, row h at out + h ldo.  No |v|^2: a block product has no
+// vanishing-vector rule.
+__device__ __forceinline__ void hvp_scatter_block_vb(const VB vb, int n, int nh, const double* __restrict__ X, int ldx,
+                                                     const int* __restrict__ inv, double* __restrict__ out, int ldo) {
+    const int p = vb.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    const int q = inv ? inv[p] : p;
+#pragma unroll
+    for (int h = 0; h < 16; ++h) {
+        const double v = (h < nh && q >= 0) ? X[(size_t)h * ldx + q] : 0.0;
+        out[(size_t)h * ldo + p] = v;
+    }
+}
+__global__ __launch_bounds__(256) void hvp_scatter_block_kernel(int n, int nh, const double* __restrict__ X, int ldx,
+                                                                const int* __restrict__ inv, double* __restrict__ out, int ldo) { hvp_scatter_block_vb(vb_hw(), n, nh, X, ldx, inv, out, ldo); }
+
+// Model kind, row vb.y of a block: hvp_model_finish's arithmetic (hv = A v + sum_j t_j S_j, the rows taken in order) on the
+// panels A V (HV) and U V (T), the free entries into row vb.y of Y
+__device__ __forceinline__ void hvp_model_finish_block_vb(const VB vb, int n, int nu, int ld, const double* __restrict__ S,
+                                                          const double* __restrict__ T, int ldt, const double* __restrict__ HV,
+                                                          int ldh, const int* __restrict__ inv, double* __restrict__ Y, int ldy) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const int p = vb.x * 256 + threadIdx.x, h = vb.y;
+    if (p >= n) return;
+    double v = HV[(size_t)h * ldh + p];
+    for (int j = 0; j < nu; ++j) v += T[(size_t)h * ldt + j] * S[(size_t)j * ld + p];
+    const int q = inv ? inv[p] : p;
+    if (q >= 0) Y[(size_t)h * ldy + q] = v;
+}
+__global__ __launch_bounds__(256) void hvp_model_finish_block_kernel(int n, int nu, int ld, const double* __restrict__ S,
+                                                                     const double* __restrict__ T, int ldt, const double* __restrict__ HV,
+                                                                     int ldh, const int* __restrict__ inv, double* __restrict__ Y, int ldy) { hvp_model_finish_block_vb(vb_hw(), n, nu, ld, S, T, ldt, HV, ldh, inv, Y, ldy); }
+
+// Model kind: diag(H)[free] = A_pp + sum_j S_j[p] u_j[p], the rows taken in order
+__device__ __forceinline__ void hvp_model_diag_vb(const VB vb, int n, int nu, int ld, const double* __restrict__ A, int lda,
+                                                  const double* __restrict__ S, const double* __restrict__ U,
+                                                  const int* __restrict__ inv, double* __restrict__ y) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const int p = vb.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    double d = A[(size_t)p * lda + p];
+    for (int j = 0; j < nu; ++j) d += S[(size_t)j * ld + p] * U[(size_t)j * ld + p];
+    const int q = inv ? inv[p] : p;
+    if (q >= 0) y[q] = d;
+}
+__global__ __launch_bounds__(256) void hvp_model_diag_kernel(int n, int nu, int ld, const double* __restrict__ A, int lda,
+                                                             const double* __restrict__ S, const double* __restrict__ U,
+                                                             const int* __restrict__ inv, double* __restrict__ y) { hvp_model_diag_vb(vb_hw(), n, nu, ld, A, lda, S, U, inv, y); }
 }  // namespace
 
 extern "C" int sella_calc_model_create(sella_ctx* c, sella_mat A, const double* U, int nu, int n, double cc, sella_calc** out) {
@@ -413,10 +468,12 @@ extern "C" int sella_fd_destroy(sella_fd* o) {
 // ---- analytic Hessian-vector operator ---------------------------------------------------------------------------------------
 // The pair record lives on the device in chunks of HVP_CHUNK products that are added as products arrive (never sized by
 // the eigensolver's iteration limit): rows [0, HVP_CHUNK) the full-space vectors, rows [HVP_CHUNK, 2 HVP_CHUNK) their
-// products, ld apart and zero beyond n, then one int per product: 1 recorded, 0 a vanishing vector.  Product number k (from
-// zero, vanishing ones included) owns row k mod HVP_CHUNK of chunk k / HVP_CHUNK, so the kernels write where the record
-// wants the result and the host learns which rows count when it asks for the pairs.
+// products, ld apart and zero beyond n, then one int per product: 1 recorded, 0 a vanishing vector.  Single product number
+// k (from zero, vanishing ones included; the rows of block products do not count here) owns row k mod HVP_CHUNK of chunk
+// k / HVP_CHUNK, so the kernels write where the record wants the result and the host learns which rows count when it asks
+// for the pairs.
 constexpr int HVP_CHUNK = 16;
+constexpr int HVP_BLOCK = 16;             // rows of a block product (the panel of sella_davidson_block)
 
 struct sella_hvp {
     sella_calc* calc = nullptr;
@@ -429,7 +486,14 @@ struct sella_hvp {
     int* inv = nullptr;
     std::vector<double*> chunks;
     std::vector<int> flags;               // host copy, valid for the first `nflags` products
-    long calls = 0;
+    long calls = 0, nrec = 0;             // products taken (rows of block products included); single products = slots of the record
+    // block products (hvp_device_apply_block), allocated with the first one: x, y of the host entry (HVP_BLOCK rows of ldm),
+    // the full-length rows of a panel with pinned coordinates (HVP_BLOCK x ld), model: A V
+    // (HVP_BLOCK x ld) and U V (HVP_BLOCK x ldt)
+    double* blk = nullptr;
+    size_t blk_bytes = 0;
+    double *bx = nullptr, *by = nullptr, *bstage = nullptr, *bhv = nullptr, *bt = nullptr;
+    int ldm = 0, ldt = 0;
 };
 
 static void hvp_release(sella_hvp* o) {
@@ -438,6 +502,7 @@ static void hvp_release(sella_hvp* o) {
     if (o->calc->kind == 1) emt_hvp_state_destroy(c, &o->emt);
     for (double* p : o->chunks) dev_free(c, p, o->chunk_bytes);
     if (o->aux) dev_free(c, o->aux, o->aux_bytes);
+    if (o->blk) dev_free(c, o->blk, o->blk_bytes);
     delete o;
 }
 
@@ -504,7 +569,7 @@ extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const
 int sella::hvp_device_apply(sella_hvp* o, const double* x, double* y) {
     sella_calc* k = o->calc;
     sella_ctx* c = k->c;
-    const long slot = o->calls;
+    const long slot = o->nrec;
     const size_t ci = (size_t)(slot / HVP_CHUNK), r = (size_t)(slot % HVP_CHUNK), ld = (size_t)o->ld;
     if (ci == o->chunks.size()) {
         double* p;
@@ -516,6 +581,7 @@ int sella::hvp_device_apply(sella_hvp* o, const double* x, double* y) {
     double *v = base + r * ld, *hv = base + (HVP_CHUNK + r) * ld;
     int* flag = reinterpret_cast<int*>(base + (size_t)2 * HVP_CHUNK * ld) + r;
     ++o->calls;
+    ++o->nrec;
     const int n = o->n;
     SELLA_LAUNCHB(c, hvp_scatter_kernel, hvp_scatter_vb, 256, dim3(o->nb), dim3(256), 0, n, x, (const int*)o->inv, v, o->part);
     if (k->kind == 1) return emt_hvp_state_apply(c, o->emt, v, hv, o->part, o->nb, o->inv, y, flag);
@@ -532,8 +598,116 @@ int sella::hvp_device_apply(sella_hvp* o, const double* x, double* y) {
     return SELLA_OK;
 }
 
+static int hvp_block_buffers(sella_hvp* o) {
+    if (o->blk) return SELLA_OK;
+    sella_calc* k = o->calc;
+    sella_ctx* c = k->c;
+    const bool model = k->kind == 0;
+    o->ldm = round_up(o->m, 8);
+    o->ldt = round_up(model && k->nu > 0 ? k->nu : 1, 8);
+    const size_t panel = (size_t)HVP_BLOCK * o->ld;
+    const size_t words = (size_t)2 * HVP_BLOCK * o->ldm + panel + (model ? panel + (size_t)HVP_BLOCK * o->ldt : 0);
+    double* p;
+    SCHK(dev_alloc(c, words * sizeof(double), &p));
+    if (s_memset0(c, p, words * sizeof(double)) != hipSuccess) {          // (the padding of the rows stays zero: panel operands)
+        dev_free(c, p, words * sizeof(double));
+        return SELLA_E_HIP;
+    }
+    o->blk = p;
+    o->blk_bytes = words * sizeof(double);
+    o->bx = p; o->by = o->bx + (size_t)HVP_BLOCK * o->ldm; o->bstage = o->by + (size_t)HVP_BLOCK * o->ldm;
+    o->bhv = o->bstage + panel; o->bt = o->bhv + panel;
+    return SELLA_OK;
+}
+
+// Y[h] = (H vfull_h)[free] for the nh <= 16 rows of the device panel X (m entries each, rows ldx / ldy apart), vfull_h zero on
+// the pinned coordinates: queued on the context's stream, nothing waited for, nothing copied.  nh calls; not entered in the
+// pair record (that belongs to the secant update of PES.diag), and no vanishing-vector rule: a zero row gives a zero row.
+// EMT: the block kernels of emt_hessian.hip on the resident state, reading X where it stands unless coordinates are pinned
+// (a scatter into full-length rows).  Model: A V and U V on the matrix cores
+// (launch_panel16, whose operand rows are as long as A's: X itself only if ldx is A's leading dimension and all are free).
+int sella::hvp_device_apply_block(sella_hvp* o, const double* X, int ldx, int nh, double* Y, int ldy) {
+    sella_calc* k = o->calc;
+    sella_ctx* c = k->c;
+    if (!X || !Y || nh < 1 || nh > HVP_BLOCK || ldx < o->m || ldy < o->m) {
+        set_error("hvp operator: a block product takes 1 to %d rows of at least %d entries", HVP_BLOCK, o->m);
+        return SELLA_E_INVALID;
+    }
+    SCHK(hvp_block_buffers(o));
+    const int n = o->n;
+    Mat* A = nullptr;
+    if (k->kind == 0) {
+        A = mat_get(c, k->A);
+        if (!A || A->ld != o->ld) {
+            set_error("hvp operator: the model calculator's matrix A is gone");
+            return SELLA_E_INVALID;
+        }
+    }
+    o->calls += nh;
+    const double* V = X;
+    int ldv = ldx;
+    if (o->inv || (k->kind == 0 && ldx != o->ld)) {
+        ldv = o->ld;
+        SELLA_LAUNCHB(c, hvp_scatter_block_kernel, hvp_scatter_block_vb, 256, dim3(o->nb), dim3(256), 0, n, nh, X, ldx,
+                      (const int*)o->inv, o->bstage, ldv);
+        V = o->bstage;
+    }
+    if (k->kind == 1) return emt_hvp_state_apply_block(c, o->emt, V, ldv, nh, o->inv, Y, ldy);
+    SCHK(launch_panel16(c, A->d, n, n, A->ld, V, nh, o->bhv, o->ld));
+    if (k->nu > 0) SCHK(launch_panel16(c, k->dconst, k->nu, n, o->ld, V, nh, o->bt, o->ldt));
+    SELLA_LAUNCHB(c, hvp_model_finish_block_kernel, hvp_model_finish_block_vb, 256, dim3(o->nb, nh), dim3(256), 0, n, k->nu, o->ld,
+                  (const double*)o->S, (const double*)o->bt, o->ldt, (const double*)o->bhv, o->ld, (const int*)o->inv, Y, ldy);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
 int sella::hvp_dim(const sella_hvp* o) { return o->m; }
+long sella::hvp_calls(const sella_hvp* o) { return o->calls; }
 sella_ctx* sella::hvp_ctx(const sella_hvp* o) { return o->calc->c; }
+
+// host panels: V, HV (k, m), any k >= 1, through the device block path in chunks of 16 rows
+extern "C" int sella_hvp_apply_block(sella_hvp* o, const double* V, int k, double* HV) {
+    if (!o || !V || !HV || k <= 0) {
+        set_error("hvp operator: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    sella_ctx* c = o->calc->c;
+    SCHK(hvp_block_buffers(o));
+    const size_t m = (size_t)o->m, ldm = (size_t)o->ldm;
+    for (int r0 = 0; r0 < k; r0 += HVP_BLOCK) {
+        const int nh = std::min(HVP_BLOCK, k - r0);
+        for (int h = 0; h < nh; ++h) SCHK(h2d_async(c, o->bx + h * ldm, V + (r0 + h) * m, m * sizeof(double)));
+        if (nh < HVP_BLOCK) HIPCHK(s_memset0(c, o->bx + nh * ldm, (HVP_BLOCK - nh) * ldm * sizeof(double)));
+        SCHK(hvp_device_apply_block(o, o->bx, o->ldm, nh, o->by, o->ldm));
+        SCHK(d2h_async_2d(c, HV + r0 * m, o->by, ldm * sizeof(double), m * sizeof(double), (size_t)nh));
+        SCHK(stream_wait(c));
+    }
+    return SELLA_OK;
+}
+
+// diag(H)[free] at the operator's geometry (m entries, host).  Not a force call and not a product.
+extern "C" int sella_hvp_diag(sella_hvp* o, double* diag) {
+    if (!o || !diag) {
+        set_error("hvp operator: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    sella_calc* k = o->calc;
+    sella_ctx* c = k->c;
+    if (k->kind == 1) {
+        SCHK(emt_hvp_state_diag(c, o->emt, o->inv, o->dy));
+    } else {
+        Mat* A = mat_get(c, k->A);
+        if (!A) {
+            set_error("hvp operator: the model calculator's matrix A is gone");
+            return SELLA_E_INVALID;
+        }
+        SELLA_LAUNCHB(c, hvp_model_diag_kernel, hvp_model_diag_vb, 256, dim3(o->nb), dim3(256), 0, o->n, k->nu, o->ld,
+                      (const double*)A->d, A->ld, (const double*)o->S, (const double*)k->dconst, (const int*)o->inv, o->dy);
+        HIPCHK(hipGetLastError());
+    }
+    SCHK(d2h_async(c, diag, o->dy, (size_t)o->m * sizeof(double)));
+    return stream_wait(c);
+}
 
 // sella_matvec_fn: host vectors — upload, the device product, download, wait
 extern "C" int sella_hvp_matvec(void* user, const double* v, double* Av, int m) {
@@ -552,7 +726,7 @@ extern "C" int sella_hvp_matvec(void* user, const double* v, double* Av, int m) 
 // which products are recorded: the flags of the products since the last look, one wait
 static int hvp_sync_flags(sella_hvp* o) {
     sella_ctx* c = o->calc->c;
-    const size_t have = o->flags.size(), want = (size_t)o->calls;
+    const size_t have = o->flags.size(), want = (size_t)o->nrec;
     if (have == want) return SELLA_OK;
     o->flags.resize(want);
     for (size_t ci = have / HVP_CHUNK; ci * HVP_CHUNK < want; ++ci) {

@@ -8,7 +8,11 @@
 // (`panel16_mfma_kernel`, kernels.hip) and expands the subspace by a block.  Parity target: the converged
 // eigenpairs equal those of exact() (sella/eigensolvers.py:9-28) — there is no trajectory to match.
 //
-// Structure of one iteration (all panels vector-major, k rows x n, same leading dimension as the matrix):
+// The operator is the resident matrix or — sella_davidson_block_hvp — the analytic Hessian-vector operator of calc.hip,
+// reached through apply_A() alone: the batched exact product on the same 16-row panels, no n x n storage.
+//
+// Structure of one iteration (all panels vector-major, k rows x n, the leading dimension of the matrix; round_up(n, 8)
+// with the matrix-free operator):
 //   Rayleigh-Ritz on the host (k x k, G = V^T A V kept incrementally);
 //   residuals of the lowest `nev` Ritz pairs  R = (AV) W - (V W) diag(theta)        [2 combine launches]
 //   correction  T = (P - theta)^-1 R  through the eigenbasis of P (two 16-RHS panel products), a diagonal,
@@ -286,6 +290,7 @@ struct Blk {
     sella_ctx* c = nullptr;
     int n = 0, ld = 0, maxvec = 0, k = 0;
     const Mat* A = nullptr;
+    sella_hvp* op = nullptr;       // instead of A: the matrix-free operator (single rank)
     int row0 = 0, world = 1, m_max = 0;
     sella_allgather_fn gather = nullptr;
     void* user = nullptr;
@@ -388,6 +393,7 @@ int put_coeffs(Blk& s, const vec& Ch, int nh, int k) {
 int apply_A(Blk& s, const double* X, int nh, double* Y, bool count = true) {
     sella_ctx* c = s.c;
     if (count) s.nmatvec += nh;
+    if (s.op) return hvp_device_apply_block(s.op, X, s.ld, nh, Y, s.ld);
     if (!s.gather) return launch_panel16(c, s.A->d, s.n, s.n, s.ld, X, nh, Y, s.ld);
     SCHK(launch_panel16(c, s.A->d, s.A->rows, s.n, s.ld, X, nh, s.send, s.m_max));
     {
@@ -981,11 +987,12 @@ int run_pipelined(Blk& s, BlkRun& r, int nev, int block, double tol, int maxiter
 
 using namespace sella;
 
-extern "C" int sella_davidson_block(sella_ctx* c, sella_mat hA, int n, int row0, int world,
-                                    sella_allgather_fn gather, void* user, sella_mat hPvecs, sella_mat hPvecsT,
-                                    const double* pevals, const double* diag, const double* V0, int nv0, int nev,
-                                    int block, int maxvec, double tol, int maxiter, double* lams_out, double* V_out,
-                                    double* res_out, int* niter_out, int* nmatvec_out, int* nconv_out) {
+// sella_davidson_block and sella_davidson_block_hvp: hA or op is the operator
+static int davidson_block_run(sella_ctx* c, sella_mat hA, sella_hvp* op, int n, int row0, int world,
+                              sella_allgather_fn gather, void* user, sella_mat hPvecs, sella_mat hPvecsT,
+                              const double* pevals, const double* diag, const double* V0, int nv0, int nev,
+                              int block, int maxvec, double tol, int maxiter, double* lams_out, double* V_out,
+                              double* res_out, int* niter_out, int* nmatvec_out, int* nconv_out) {
     if (!c || n <= 0 || nev <= 0 || !lams_out || !V_out) {
         set_error("davidson_block: invalid arguments");
         return SELLA_E_INVALID;
@@ -1009,24 +1016,30 @@ extern "C" int sella_davidson_block(sella_ctx* c, sella_mat hA, int n, int row0,
     Blk s;
     s.c = c;
     s.n = n;
-    s.A = mat_get(c, hA);
-    if (!s.A) return SELLA_E_INVALID;
-    s.ld = s.A->ld;
-    if (s.A->cols != n) { set_error("davidson_block: the operator must have %d columns", n); return SELLA_E_INVALID; }
-    s.gather = gather;
-    s.user = user;
-    s.row0 = row0;
-    s.world = (world > 0) ? world : 1;
-    if (gather) {
-        s.m_max = (n + s.world - 1) / s.world;
-        if (s.A->rows > s.m_max || row0 < 0 || row0 + s.A->rows > n || row0 % s.m_max != 0) {
-            set_error("davidson_block: row panel [%d, %d) does not fit the sharding %d x %d", row0, row0 + s.A->rows,
-                      s.world, s.m_max);
+    s.op = op;
+    const long calls0 = op ? hvp_calls(op) : 0;
+    if (op) {
+        s.ld = round_up(n, 8);             // the panels' own row stride: there is no matrix to share one with
+    } else {
+        s.A = mat_get(c, hA);
+        if (!s.A) return SELLA_E_INVALID;
+        s.ld = s.A->ld;
+        if (s.A->cols != n) { set_error("davidson_block: the operator must have %d columns", n); return SELLA_E_INVALID; }
+        s.gather = gather;
+        s.user = user;
+        s.row0 = row0;
+        s.world = (world > 0) ? world : 1;
+        if (gather) {
+            s.m_max = (n + s.world - 1) / s.world;
+            if (s.A->rows > s.m_max || row0 < 0 || row0 + s.A->rows > n || row0 % s.m_max != 0) {
+                set_error("davidson_block: row panel [%d, %d) does not fit the sharding %d x %d", row0, row0 + s.A->rows,
+                          s.world, s.m_max);
+                return SELLA_E_INVALID;
+            }
+        } else if (s.A->rows != n || row0 != 0) {
+            set_error("davidson_block: without an all-gather the operator must hold all %d rows", n);
             return SELLA_E_INVALID;
         }
-    } else if (s.A->rows != n || row0 != 0) {
-        set_error("davidson_block: without an all-gather the operator must hold all %d rows", n);
-        return SELLA_E_INVALID;
     }
     if (hPvecs != SELLA_NO_MAT) {
         s.Q = mat_get(c, hPvecs);
@@ -1292,7 +1305,9 @@ extern "C" int sella_davidson_block(sella_ctx* c, sella_mat hA, int n, int row0,
             for (int h = 0; h < nh; ++h) V_out[(size_t)i * nev + j0 + h] = Xh[(size_t)h * n + i];
     }
     if (niter_out) *niter_out = iter;
-    if (nmatvec_out) *nmatvec_out = s.nmatvec;
+    // (the matrix-free operator counts for itself: every row it was applied to, the early passes over converged pairs and the
+    // refreshes of AV included)
+    if (nmatvec_out) *nmatvec_out = op ? (int)(hvp_calls(op) - calls0) : s.nmatvec;
     if (nconv_out) *nconv_out = done ? nev : nconv;
     const double ts4 = bd_now_us();
     blk_free(s);
@@ -1302,4 +1317,31 @@ extern "C" int sella_davidson_block(sella_ctx* c, sella_mat hA, int n, int row0,
     return SELLA_OK;
 #undef BCHK
 #undef BHIP
+}
+
+extern "C" int sella_davidson_block(sella_ctx* c, sella_mat hA, int n, int row0, int world,
+                                    sella_allgather_fn gather, void* user, sella_mat hPvecs, sella_mat hPvecsT,
+                                    const double* pevals, const double* diag, const double* V0, int nv0, int nev,
+                                    int block, int maxvec, double tol, int maxiter, double* lams_out, double* V_out,
+                                    double* res_out, int* niter_out, int* nmatvec_out, int* nconv_out) {
+    return davidson_block_run(c, hA, nullptr, n, row0, world, gather, user, hPvecs, hPvecsT, pevals, diag, V0, nv0, nev, block,
+                              maxvec, tol, maxiter, lams_out, V_out, res_out, niter_out, nmatvec_out, nconv_out);
+}
+
+extern "C" int sella_davidson_block_hvp(sella_ctx* c, sella_hvp* op, sella_mat hPvecs, sella_mat hPvecsT, const double* pevals,
+                                        const double* diag, const double* V0, int nv0, int nev, int block, int maxvec,
+                                        double tol, int maxiter, double* lams_out, double* V_out, double* res_out,
+                                        int* niter_out, int* nmatvec_out, int* nconv_out) {
+    if (!c || !op || hvp_ctx(op) != c) {
+        set_error("davidson_block: the Hessian-vector operator must belong to this context");
+        return SELLA_E_INVALID;
+    }
+    const int m = hvp_dim(op);
+    if (nev <= 0 || nev > m || block < 1 || block > BD_NB || nv0 > BD_NB || nv0 < 0) {
+        set_error("davidson_block: with the Hessian-vector operator 1 <= nev <= %d, 1 <= block <= %d and at most %d start vectors",
+                  m, BD_NB, BD_NB);
+        return SELLA_E_INVALID;
+    }
+    return davidson_block_run(c, SELLA_NO_MAT, op, m, 0, 1, nullptr, nullptr, hPvecs, hPvecsT, pevals, diag, V0, nv0, nev, block,
+                              maxvec, tol, maxiter, lams_out, V_out, res_out, niter_out, nmatvec_out, nconv_out);
 }

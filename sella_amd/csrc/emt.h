@@ -47,7 +47,8 @@ int emt_density_queue(sella_ctx* c, int n, const double* pos, const double* par,
                       EmtArgs* args, double** extra);
 
 // emt_hessian.hip: what the Hessian-vector operator (calc.hip, sella_hvp) keeps of a geometry — the argument block of the
-// density pass with its arrays, F2 and room for the n dots of a product, in ONE allocation of the state's own.
+// density pass with its arrays, F2 and room for the dots of a product (n of one vector in front, 16 n of a block of
+// vectors), in ONE allocation of the state's own.
 struct EmtHvpState {
     EmtArgs a;
     double* F2 = nullptr;
@@ -60,5 +61,10 @@ int emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const double* p
 void emt_hvp_state_destroy(sella_ctx* c, EmtHvpState* st);
 int emt_hvp_state_apply(sella_ctx* c, const EmtHvpState& st, const double* v, double* hv, const double* part, int nb,
                         const int* inv, double* y, int* flag);
+// the same for the nh <= 16 rows of a device panel (row h at V + h ldv, full length), the free rows written into Y (row h at
+// Y + h ldy), and diag(H)[free] into y
+int emt_hvp_state_apply_block(sella_ctx* c, const EmtHvpState& st, const double* V, int ldv, int nh, const int* inv, double* Y,
+                              int ldy);
+int emt_hvp_state_diag(sella_ctx* c, const EmtHvpState& st, const int* inv, double* y);
 
 }  // namespace sella

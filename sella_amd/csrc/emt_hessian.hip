@@ -20,6 +20,9 @@
 //   operator: the same two product kernels for ONE vector (emt_hvp1_dots, emt_hvp1_gather: 3 accumulators per thread instead
 //            of 24) on a state that is built once per geometry and owned by the operator (EmtHvpState: positions, sigma1,
 //            dEdsig, the lists, F2), device vector in, device vector out, nothing waited for (calc.hip, sella_hvp_*)
+//   block:   the product for the up to 16 rows of a device panel on the same state (emt_hvpb_dots, emt_hvpb_gather: all 16
+//            vectors in one workgroup per atom; the free rows written straight into the caller's panel), and the diagonal
+//            of H (emt_hdiag) — the operator of the block Davidson
 // No atomics: an atom can be a neighbour through several images, and those visits belong to different threads unless
 // 256 divides N, so everything that lands in a shared place is added image by image with a barrier in between (one
 // writer per (i, j) within an image, images in index order); per-thread sums run in the order of the lists and are
@@ -323,6 +326,179 @@ __device__ __forceinline__ void emt_hvp1_gather_vb(const VB vb, EmtArgs a, EmtHv
 }
 __global__ __launch_bounds__(256) void emt_hvp1_gather_kernel(EmtArgs a, EmtHvp o, EmtHvpOut1 w) { emt_hvp1_gather_vb(vb_hw(), a, o, w); }
 
+// ---- the block product of the operator (calc.hip, hvp_device_apply_block) -------------------------------------------------
+// Up to HVB_W vectors, the rows of a device panel (row h at V + h ldv: the eigensolver's own panel when all 3n coordinates
+// are free, else the full-length rows a scatter filled), on the operator's resident state.  One workgroup per atom carries
+// all HVB_W vectors: the pair quantities of a visit are evaluated once for all of them (48 accumulators per thread in the
+// gather pass; 8 per workgroup, and a panel staged atom-major, were measured and lost: profiles/block_hvp.md).  The dots
+// c_j are kept atom-major.  Rows beyond nh are never read (the row index is clamped: their slots repeat row nh - 1 and are
+// not stored).  Every vector's sums are taken in the order of the single-vector kernels and every product is rounded on its
+// own (no contraction into fused multiply-adds, which the compiler chooses slot by slot in the unrolled loops: measured, the
+// same vector in slot 0 and in slot 11 differed in the last bit), so a row's result does not depend on which row it is, on
+// what stands in the other rows, or on nh.
+constexpr int HVB_W = 16;
+
+struct EmtHvpB {
+    const double* F2;
+    const double* V; int ldv;               // the panel
+    int nh;
+    double* cdot;                           // n x HVB_W: c_j of vector q at [HVB_W j + q]
+    const int* inv;                         // full coordinate -> column of Y, -1 if pinned; null: all free
+    double* Y; int ldy;                     // (nh, m): the free rows of the products
+};
+
+__device__ __forceinline__ void hvb_load(const EmtHvpB& o, int q, int j, double& x, double& y, double& z) {
+    const double* v = o.V + (size_t)(q < o.nh ? q : o.nh - 1) * o.ldv + 3 * j;
+    x = v[0]; y = v[1]; z = v[2];
+}
+
+// block_sum's arithmetic for NS sums behind ONE barrier (as emt_cell_pair): the wavefronts' sums side by side in LDS; after
+// the barrier thread t < NS reads sum t with hvb_total
+template <int NS>
+__device__ __forceinline__ void hvb_put(double (*part)[NS], int slot, double v) {
+    v = wave_sum64(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][slot] = v;
+}
+template <int NS>
+__device__ __forceinline__ double hvb_total(const double (*part)[NS], int slot) {
+    return (part[0][slot] + part[1][slot]) + (part[2][slot] + part[3][slot]);
+}
+
+__device__ __forceinline__ void emt_hvpb_dots_vb(const VB vb, EmtArgs a, EmtHvpB o) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    __shared__ double part[4][HVB_W];
+    __shared__ int incomplete;
+    const int i = vb.x;
+    const EmtAtom m = emt_atom(a, i);
+    double vi[HVB_W][3], acc[HVB_W];
+#pragma unroll
+    for (int q = 0; q < HVB_W; ++q) {
+        hvb_load(o, q, i, vi[q][0], vi[q][1], vi[q][2]);
+        acc[q] = 0.0;
+    }
+    auto visit = [&](int t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        EmtPair p;
+        if (!emt_pair(a, m, t, p)) return;
+#pragma unroll
+        for (int q = 0; q < HVB_W; ++q) {
+            double v0, v1, v2;
+            hvb_load(o, q, p.j, v0, v1, v2);
+            acc[q] += p.wp_ij * (p.ux * (v0 - vi[q][0]) + p.uy * (v1 - vi[q][1]) + p.uz * (v2 - vi[q][2]));
+        }
+    };
+    emt_by_image<false>(a, i, &incomplete, visit);
+#pragma unroll
+    for (int q = 0; q < HVB_W; ++q) hvb_put<HVB_W>(part, q, acc[q]);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < HVB_W) o.cdot[(size_t)i * HVB_W + t] = hvb_total<HVB_W>(part, t);
+}
+__global__ __launch_bounds__(256) void emt_hvpb_dots_kernel(EmtArgs a, EmtHvpB o) { emt_hvpb_dots_vb(vb_hw(), a, o); }
+
+__device__ __forceinline__ void emt_hvpb_gather_vb(const VB vb, EmtArgs a, EmtHvpB o) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    __shared__ double part[4][3 * HVB_W];
+    __shared__ int incomplete;
+    const int i = vb.x;
+    const EmtAtom m = emt_atom(a, i);
+    const double f2i = o.F2[i];
+    double vi[HVB_W][3], fc[HVB_W], acc[HVB_W][3];
+#pragma unroll
+    for (int q = 0; q < HVB_W; ++q) {
+        hvb_load(o, q, i, vi[q][0], vi[q][1], vi[q][2]);
+        fc[q] = f2i * o.cdot[(size_t)i * HVB_W + q];
+        acc[q][0] = acc[q][1] = acc[q][2] = 0.0;
+    }
+    auto visit = [&](int t) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        EmtPair p;
+        if (!emt_pair(a, m, t, p)) return;
+        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;
+        const double f2j = o.F2[p.j];
+        const double* cj = o.cdot + (size_t)p.j * HVB_W;
+#pragma unroll
+        for (int q = 0; q < HVB_W; ++q) {
+            double v0, v1, v2;
+            hvb_load(o, q, p.j, v0, v1, v2);
+            const double dx = vi[q][0] - v0, dy = vi[q][1] - v1, dz = vi[q][2] - v2;
+            const double along = c2 * (p.ux * dx + p.uy * dy + p.uz * dz) - (fc[q] * p.wp_ij + f2j * cj[q] * p.wp_ji);
+            acc[q][0] += c1 * dx + along * p.ux;
+            acc[q][1] += c1 * dy + along * p.uy;
+            acc[q][2] += c1 * dz + along * p.uz;
+        }
+    };
+    emt_by_image<false>(a, i, &incomplete, visit);
+#pragma unroll
+    for (int q = 0; q < HVB_W; ++q) {
+        hvb_put<3 * HVB_W>(part, 3 * q, acc[q][0]);
+        hvb_put<3 * HVB_W>(part, 3 * q + 1, acc[q][1]);
+        hvb_put<3 * HVB_W>(part, 3 * q + 2, acc[q][2]);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= 3 * HVB_W) return;
+    const int q = t / 3, p = 3 * i + t % 3;
+    if (q >= o.nh) return;
+    const int r = o.inv ? o.inv[p] : p;
+    if (r >= 0) o.Y[(size_t)q * o.ldy + r] = hvb_total<3 * HVB_W>(part, t);
+}
+__global__ __launch_bounds__(256) void emt_hvpb_gather_kernel(EmtArgs a, EmtHvpB o) { emt_hvpb_gather_vb(vb_hw(), a, o); }
+
+// The diagonal of H on the same state: H[(i,a),(i,a)] = sum_{visits, j != i} K_aa + F2_i g_i[a]^2 + sum_{j != i} F2_j g_j[(i,a)]^2,
+// g_i[a] = -sum_visits w'_ij u_a and g_j[(i,a)] = -sum over the visits TO ATOM j of w'_ji u_a: a neighbour seen through
+// several images enters the last term with the square of its summed share, not the sum of squares, so the visits are
+// taken neighbour by neighbour here — thread t owns the atoms j = t, t + 256, ... through all their images (the sweep of
+// emt_by_image in the other order; emt_pair tests the distance itself) — and no sum crosses threads before block_sum's
+// arithmetic.  The free entries go to y (inv as above).
+__device__ __forceinline__ void emt_hdiag_vb(const VB vb, EmtArgs a, const double* __restrict__ F2, const int* __restrict__ inv,
+                                             double* __restrict__ y) {
+    __shared__ double part[4][9];
+    const int i = vb.x;
+    const EmtAtom m = emt_atom(a, i);
+    double k[3] = {0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0}, e[3] = {0.0, 0.0, 0.0};
+    for (int j = threadIdx.x; j < a.n; j += 256) {
+        double h[3] = {0.0, 0.0, 0.0};
+        for (int s = 0; s < a.nshift; ++s) {
+            EmtPair p;
+            if (!emt_pair(a, m, emt_pack(j, s), p)) continue;
+            const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
+            const double u[3] = {p.ux, p.uy, p.uz};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                k[c] += c1 + c2 * (u[c] * u[c]);
+                g[c] -= p.wp_ij * u[c];
+                h[c] -= p.wp_ji * u[c];
+            }
+        }
+        const double f2j = F2[j];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) e[c] += f2j * (h[c] * h[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        hvb_put<9>(part, c, k[c]);
+        hvb_put<9>(part, 3 + c, g[c]);
+        hvb_put<9>(part, 6 + c, e[c]);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= 3) return;
+    const double gi = hvb_total<9>(part, 3 + t);
+    const int p = 3 * i + t, r = inv ? inv[p] : p;
+    if (r >= 0) y[r] = hvb_total<9>(part, t) + F2[i] * (gi * gi) + hvb_total<9>(part, 6 + t);
+}
+__global__ __launch_bounds__(256) void emt_hdiag_kernel(EmtArgs a, const double* __restrict__ F2, const int* __restrict__ inv,
+                                                        double* __restrict__ y) { emt_hdiag_vb(vb_hw(), a, F2, inv, y); }
+
 // ---- the cell columns ---------------------------------------------------------------------------------------------------
 // symmetric index of (a, b), a, b in 0..2, in the order xx, yy, zz, yz, xz, xy
 __host__ __device__ __forceinline__ int sym6(int a, int b) { return a == b ? a : 6 - a - b; }
@@ -624,12 +800,13 @@ int sella::emt_hvp_resident(sella_ctx* c, int n, const double* pos, const double
 int sella::emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
                                 const double* dconst, double rc, double acut, double cutoff, double beta, EmtHvpState* st) {
     EmtArgs a;
-    double* ex;                                                       // F2 (n), c_i = g_i . v (n)
-    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, (size_t)2 * n, &a, &ex));
+    double* ex;                                                       // F2 (n), c_i = g_i . v (n; HVB_W n for a block product)
+    const size_t extra = (size_t)(1 + HVB_W) * n;
+    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, extra, &a, &ex));
     SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, ex);
     HIPCHK(hipGetLastError());
     const char* lo = reinterpret_cast<const char*>(a.pos);            // (the positions lead the slot)
-    const char* hi = reinterpret_cast<const char*>(ex + (size_t)2 * n);
+    const char* hi = reinterpret_cast<const char*>(ex + extra);
     st->own_bytes = (size_t)(hi - lo);
     SCHK(dev_alloc(c, st->own_bytes, &st->own));
     HIPCHK(s_memcpy(c, st->own, lo, st->own_bytes, hipMemcpyDeviceToDevice));
@@ -663,6 +840,26 @@ int sella::emt_hvp_state_apply(sella_ctx* c, const EmtHvpState& st, const double
     const dim3 grid(st.a.n);
     SELLA_LAUNCHB(c, emt_hvp1_dots_kernel, emt_hvp1_dots_vb, 256, grid, dim3(256), 0, st.a, o);
     SELLA_LAUNCHB(c, emt_hvp1_gather_kernel, emt_hvp1_gather_vb, 256, grid, dim3(256), 0, st.a, o, w);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
+// Y[h] = (H v_h)[free] for the nh <= HVB_W rows of the panel V (row h at V + h ldv, full length): two launches on the
+// context's stream, nothing waited for.
+int sella::emt_hvp_state_apply_block(sella_ctx* c, const EmtHvpState& st, const double* V, int ldv, int nh, const int* inv,
+                                     double* Y, int ldy) {
+    EmtHvpB o;
+    o.F2 = st.F2; o.V = V; o.ldv = ldv; o.nh = nh; o.cdot = st.cdot; o.inv = inv; o.Y = Y; o.ldy = ldy;
+    const dim3 grid(st.a.n);
+    SELLA_LAUNCHB(c, emt_hvpb_dots_kernel, emt_hvpb_dots_vb, 256, grid, dim3(256), 0, st.a, o);
+    SELLA_LAUNCHB(c, emt_hvpb_gather_kernel, emt_hvpb_gather_vb, 256, grid, dim3(256), 0, st.a, o);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
+// y = diag(H)[free] on the device: one launch, nothing waited for
+int sella::emt_hvp_state_diag(sella_ctx* c, const EmtHvpState& st, const int* inv, double* y) {
+    SELLA_LAUNCHB(c, emt_hdiag_kernel, emt_hdiag_vb, 256, dim3(st.a.n), dim3(256), 0, st.a, (const double*)st.F2, inv, y);
     HIPCHK(hipGetLastError());
     return SELLA_OK;
 }

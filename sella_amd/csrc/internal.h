@@ -395,6 +395,10 @@ double calc_finish(sella_calc* k, const double* x, const double* aux_host);
 // the analytic Hessian-vector operator (calc.hip, sella_hvp_*) as sella_davidson_hvp sees it: y = (H vfull)[free] for device
 // vectors of hvp_dim() entries, queued on the stream of hvp_ctx(), nothing waited for
 int hvp_device_apply(sella_hvp* op, const double* x, double* y);
+// the same for the nh <= 16 rows of a device panel (m entries each, ldx / ldy apart), as sella_davidson_block_hvp sees it:
+// nh calls, not entered in the pair record
+int hvp_device_apply_block(sella_hvp* op, const double* X, int ldx, int nh, double* Y, int ldy);
+long hvp_calls(const sella_hvp* op);
 int hvp_dim(const sella_hvp* op);
 sella_ctx* hvp_ctx(const sella_hvp* op);
 // stepper.hip: step family on m modes = rows idx[0..m) of a device panel (gathered into matrices the stepper owns)

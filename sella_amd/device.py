@@ -349,11 +349,24 @@ class Context:
         kk = k.value
         return (lams[:kk], V[:n * kk].reshape(n, kk), AV[:n * kk].reshape(n, kk), nmv.value)
 
-    def davidson_block(self, A, n, nev, block=16, tol=1e-8, maxiter=500, maxvec=0, V0=None, Pvecs=None,
+    def davidson_block(self, A, n=None, nev=1, block=16, tol=1e-8, maxiter=500, maxvec=0, V0=None, Pvecs=None,
                        PvecsT=None, pevals=None, diag=None, row0=0, world=1, allgather=None):
         """Lowest `nev` eigenpairs by block Davidson (csrc/davidson_block.hip).  A: DeviceMatrix (n x n), or this
         rank's row panel with `allgather(send_ptr, recv_ptr, nbytes, stream_ptr) -> None` assembling the block
-        product over the ranks.  Returns dict(lams, V (n x nev), res, niter, nmatvec, nconv)."""
+        product over the ranks, or a `DeviceHvpOperator` (`sella_davidson_block_hvp`: the batched exact products, no
+        n x n storage; one rank, `n` may be left out).  Returns dict(lams, V (n x nev), res, niter, nmatvec, nconv).
+        `nmatvec`: with a matrix, the columns the iteration asked for; with a `DeviceHvpOperator`, every row the operator was
+        applied to (the growth of `A.calls`: the early passes over converged pairs and the refreshes of A V included), so the
+        two are not comparable."""
+        matrix_free = isinstance(A, DeviceHvpOperator)
+        if matrix_free:
+            if n is not None and int(n) != A.shape[0]:
+                raise ValueError(f'the operator has dimension {A.shape[0]}, not n = {n}')
+            if row0 != 0 or world != 1 or allgather is not None:
+                raise ValueError('a DeviceHvpOperator runs on one rank: row0 / world / allgather do not apply')
+            n = A.shape[0]
+        elif n is None:
+            raise ValueError('n is required with a resident matrix')
         lams = np.zeros(nev)
         V = np.zeros((n, nev))
         res = np.zeros(nev)
@@ -380,11 +393,13 @@ class Context:
             nv0 = v0.shape[1]
         pe = as_f64(pevals) if pevals is not None else None
         dg = as_f64(diag) if diag is not None else None
-        st = _lib.lib().sella_davidson_block(
-            self._h, A.handle, int(n), int(row0), int(world), cb, None,
-            SELLA_NO_MAT if Pvecs is None else Pvecs.handle, SELLA_NO_MAT if PvecsT is None else PvecsT.handle,
-            ptr(pe), ptr(dg), ptr(v0), nv0, int(nev), int(block), int(maxvec), float(tol), int(maxiter),
-            ptr(lams), ptr(V), ptr(res), byref(niter), byref(nmv), byref(nconv))
+        tail = (SELLA_NO_MAT if Pvecs is None else Pvecs.handle, SELLA_NO_MAT if PvecsT is None else PvecsT.handle,
+                ptr(pe), ptr(dg), ptr(v0), nv0, int(nev), int(block), int(maxvec), float(tol), int(maxiter),
+                ptr(lams), ptr(V), ptr(res), byref(niter), byref(nmv), byref(nconv))
+        if matrix_free:
+            st = _lib.lib().sella_davidson_block_hvp(self._h, A._h, *tail)
+        else:
+            st = _lib.lib().sella_davidson_block(self._h, A.handle, int(n), int(row0), int(world), cb, None, *tail)
         if err:
             raise err[0]
         check(st)
@@ -791,8 +806,10 @@ class DeviceHvpOperator:
     """The analytic Hessian of a `DeviceCalculator` at x0 as a matrix-free operator (`sella_hvp_*`): what depends on the
     geometry is built once and stays on the device, a product is exact and is not a force call.  `free`: the coordinates
     the eigensolver sees (ascending; None: all).  Passed to `Context.davidson` as the operator (`sella_davidson_hvp`: the
-    products stay on the device); `apply(v)` is one product with host vectors; `Vs` / `AVs` afterwards hold the recorded
-    pairs (full space, one column per product of a non-vanishing vector), like `DeviceFdOperator`.  `through_host=True`
+    products stay on the device) or to `Context.davidson_block` (`sella_davidson_block_hvp`: several lowest pairs from
+    batched products); `apply(v)` is one product with host vectors, `apply_block(V)` the batched products of the rows of V,
+    `diagonal()` the diagonal; `Vs` / `AVs` afterwards hold the recorded pairs of the single products (full space, one
+    column per product of a non-vanishing vector), like `DeviceFdOperator`.  `through_host=True`
     makes `Context.davidson` run the unchanged `sella_davidson` with `sella_hvp_matvec` as its host callback instead (same
     results; for comparisons and measurements)."""
 
@@ -825,6 +842,22 @@ class DeviceHvpOperator:
 
     dot = apply
     calls = property(lambda self: int(_lib.lib().sella_hvp_calls(self._h)))
+
+    def apply_block(self, V):
+        """The products of the rows of V (k, m), any k >= 1, through the batched device kernels in chunks of 16 rows
+        (`sella_hvp_apply_block`): (k, m).  k calls; block products are not entered in `Vs` / `AVs`."""
+        V = np.ascontiguousarray(as_f64(V))
+        if V.ndim != 2 or V.shape[0] == 0 or V.shape[1] != self.shape[0]:
+            raise ValueError(f'expected vectors of length {self.shape[0]} as an array of shape (k, {self.shape[0]}), got {V.shape}')
+        out = np.empty_like(V)
+        check(_lib.lib().sella_hvp_apply_block(self._h, ptr(V), V.shape[0], ptr(out)))
+        return out
+
+    def diagonal(self):
+        """diag(H)[free] at the operator's geometry (`sella_hvp_diag`), (m,): neither a force call nor a product."""
+        out = np.empty(self.shape[0])
+        check(_lib.lib().sella_hvp_diag(self._h, ptr(out)))
+        return out
 
     def _pairs(self):
         k = int(_lib.lib().sella_hvp_npairs(self._h))

@@ -222,3 +222,73 @@ def block_davidson(A, nev, P=None, tol=1e-8, block=16, maxiter=500, maxvec=0, v0
     if out['nconv'] < nev:
         raise RuntimeError(f'block_davidson: {out["nconv"]} of {nev} pairs converged in {out["niter"]} iterations')
     return out['lams'], out['V'], out['res']
+
+
+def _free_coordinates(atoms, constraints, free):
+    """Ascending free Cartesian coordinates (int32) of `lowest_modes`, or None when nothing is pinned."""
+    n = 3 * len(atoms)
+    if free is not None and constraints is not None:
+        raise ValueError('lowest_modes: give the free coordinates as `free` or as `constraints`, not both')
+    if free is not None:
+        free = np.asarray(free)
+        if free.ndim != 1 or free.size == 0 or not np.issubdtype(free.dtype, np.integer):
+            raise ValueError('lowest_modes: `free` must be a non-empty list of coordinate indices')
+        if free[0] < 0 or free[-1] >= n or np.any(np.diff(free) <= 0):
+            raise ValueError(f'lowest_modes: `free` must be ascending indices below {n}')
+        return free.astype(np.int32)
+    if constraints is None:
+        return None
+    from .peswrapper import _pinned_coordinates
+    from .search import _only_translations
+    c = constraints
+    if not _only_translations(c):
+        raise NotImplementedError('lowest_modes: only constraints that pin Cartesian coordinates (fix_translation on single '
+                                  'atoms) select coordinates; curved or inequality constraints are not covered')
+    drdx = c.jacobian()
+    if drdx.shape[0] == 0:
+        return None
+    pinned = _pinned_coordinates(drdx)
+    if pinned is None:
+        raise NotImplementedError('lowest_modes: the constraints are not a selection of Cartesian coordinates')
+    return np.setdiff1d(np.arange(n), pinned[0]).astype(np.int32)
+
+
+def lowest_modes(atoms, nev=1, constraints=None, free=None, tol=1e-8, block=None, maxiter=500, maxvec=0, V0=None,
+                 allow_unconverged=False):
+    """The `nev` lowest curvatures and modes of the Hessian of `atoms` over its free coordinates, without the 3N x 3N
+    matrix: block Davidson (`sella_davidson_block_hvp`) on the analytic Hessian-vector operator of a calculator that lives
+    in the library (device `EMT`, `QuadraticCubicModel` with a device matrix), preconditioned with the operator's diagonal.
+
+    The free coordinates are `free` (ascending indices into the 3N Cartesian coordinates) or what a `Constraints` object
+    that pins coordinates (`fix_translation`) leaves; default: all.  V0: (m, k <= 16) start block over the free coordinates.
+    Returns dict(lams (nev,), modes (nev, N, 3), res, niter, nmatvec, nconv); `modes` are orthonormal and zero on the
+    pinned coordinates.
+
+    A pair counts as converged when |r| <= tol |theta|: the rule is RELATIVE, so an exact zero mode never converges.  A
+    system that has them — nothing pinned in a periodic cell (three translations), a free cluster (six) — should have
+    atoms pinned, which removes them; otherwise `nconv < nev` raises RuntimeError unless `allow_unconverged=True`."""
+    from .atoms import supports_hessian
+    calc = getattr(atoms, 'calc', None)
+    if not (supports_hessian(calc) and getattr(calc, 'library_form', False)):
+        raise NotImplementedError(f'lowest_modes: {type(calc).__name__} has no analytic Hessian-vector operator in the library '
+                                  '(device EMT and QuadraticCubicModel with a device matrix have)')
+    n = 3 * len(atoms)
+    sel = _free_coordinates(atoms, constraints, free)
+    m = n if sel is None else len(sel)
+    nev = int(nev)
+    if nev < 1 or nev > m:
+        raise ValueError(f'lowest_modes: nev = {nev} with {m} free coordinates')
+    if block is None:
+        block = min(16, max(nev, 4))
+    atoms.get_potential_energy()                                       # the evaluation the library calculator is made at
+    dc = calc.device_calculator()
+    op = DeviceHvpOperator(dc, np.asarray(atoms.positions, dtype=np.float64).ravel(), sel)
+    out = dc.ctx.davidson_block(op, None, nev, block=min(int(block), m), tol=tol, maxiter=maxiter, maxvec=maxvec, V0=V0,
+                                diag=op.diagonal())
+    if out['nconv'] < nev and not allow_unconverged:
+        raise RuntimeError(f'lowest_modes: nconv = {out["nconv"]} of {nev} pairs converged in {out["niter"]} iterations '
+                           '(the stopping rule is relative: zero modes do not converge; pin atoms)')
+    modes = np.zeros((nev, n))
+    modes[:, np.arange(n) if sel is None else sel] = out['V'].T
+    return dict(lams=out['lams'], modes=modes.reshape(nev, len(atoms), 3), res=out['res'], niter=out['niter'],
+                nmatvec=out['nmatvec'], nconv=out['nconv'])

@@ -37,6 +37,12 @@ _COVERED = {'order', 'eta', 'gamma', 'delta0', 'sigma_inc', 'sigma_dec', 'rho_in
             'trajectory', 'internal'}
 
 
+def _only_translations(c):
+    """Whether the constraint set `c` holds nothing but equality constraints on translations — what a selection of Cartesian
+    coordinates can be made of (no bonds, angles, dihedrals, rotations or inequalities)."""
+    return not ((c.nbonds + c.nangles + c.ndihedrals) > 0 or c.has_inequalities() or c.internals['rotations'])
+
+
 def _pinned_free(atoms, constraints, proj_trans, proj_rot):
     """Free coordinates of a constraint set made of single-coordinate pins — None: unconstrained; False: not covered
     (the defaults of `PES.__init__`, peswrapper.py:236-253, add a global translation / rotation constraint, whose
@@ -48,7 +54,7 @@ def _pinned_free(atoms, constraints, proj_trans, proj_rot):
     if constraints is None:
         return None
     c = constraints
-    if (c.nbonds + c.nangles + c.ndihedrals) > 0 or c.has_inequalities() or c.internals['rotations']:
+    if not _only_translations(c):
         return False
     # (asked three times per search — `applies` twice, the constructor once — with a dense constraint Jacobian each time:
     # 4 ms of interpreter time per 256-atom ensemble member, serial under the interpreter lock; remembered per constraint
