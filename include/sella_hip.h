@@ -499,6 +499,17 @@ int sella_emt_hvp(sella_ctx* ctx, int n, const double* pos, const double* par, i
 int sella_emt_cell_hessian(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
                            const double* shifts, const double* cell, double rc, double acut, double cutoff, double beta,
                            sella_mat out);
+/* Products with that Hessian without forming it: HV[q] = H V[q] for k vectors, V and HV (k x (3n + 9)) host arrays with
+ * one vector [v (3n); W.ravel() (9, W the variation of C)] per row, in the coordinates of sella_emt_cell_hessian.  A
+ * direction displaces the pair of a visit by v_j - v_i + n_s W; the two passes of sella_emt_hvp with that displacement
+ * give the position rows, the same pair quantities contracted with the image indices the nine cell rows, summed over the
+ * atoms in a fixed order.  No storage of size (3n)^2 or (3n + 9)^2, no atomics, the same bit for bit from call to call
+ * and whether or not the neighbour lists overflowed; any k >= 1 (four vectors per workgroup, all groups in one launch
+ * of each pass).  A null pointer, n, k or nshift <= 0, nshift > 127, a singular cell, or a shift whose image index is
+ * not whole to 1e-6: SELLA_E_INVALID.                                                                                */
+int sella_emt_cell_hvp(sella_ctx* ctx, int n, const double* pos, const double* par, int nshift,
+                       const double* shifts, const double* cell, double rc, double acut, double cutoff, double beta,
+                       const double* V, int k, double* HV);
 
 /* ---- calculators that live in the library, and the finite-difference Hessian on top of one ----------------- */
 /* sella/peswrapper.py:413-418 evaluates energy and forces through `atoms.calc`; for a calculator implemented HERE that

@@ -197,6 +197,8 @@ SIGNATURES = {
                               c_double, c_void_p, c_int, c_void_p]),
     'sella_emt_cell_hessian': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double,
                                        c_double, c_double, c_int]),
+    'sella_emt_cell_hvp': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double,
+                                   c_double, c_double, c_void_p, c_int, c_void_p]),
     'sella_prof_enable': (c_int, [c_void_p, c_int]),
     'sella_prof_reset': (c_int, [c_void_p]),
     'sella_prof_get': (c_int, [c_void_p, c_int, POINTER(c_long), c_double_p, c_double_p, c_double_p]),

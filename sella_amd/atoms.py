@@ -249,6 +249,17 @@ def supports_cell_hessian(calc):
     return callable(getattr(calc, 'get_cell_hessian', None))
 
 
+def supports_cell_hvp(calc):
+    """Whether `calc` can multiply the Hessian of positions and cell into vectors without forming it
+    (`cell_hessian_vector_product`): a calculator of this module that implements `cell_hessian_products`, or a foreign
+    calculator with a `cell_hessian_vector_product` method."""
+    if calc is None:
+        return False
+    if isinstance(calc, Calculator):
+        return calc.has_cell_hvp
+    return callable(getattr(calc, 'cell_hessian_vector_product', None))
+
+
 class Calculator:
     """energy_and_gradient(positions (N,3)) -> (E, dE/dx (N,3)); results cached per geometry (positions and cell).
     A calculator that also has the virial implements energy_gradient_virial(positions) -> (E, dE/dx, W (6,)), W the
@@ -261,7 +272,10 @@ class Calculator:
     device_cell_hessian(positions, cell) -> (3N + 9)-square `DeviceMatrix` in the coordinates [positions; cell.ravel()]
     (lattice vectors in the rows of the cell, positions fixed while the cell varies); get_cell_hessian() and
     get_device_cell_hessian() are then available (and fit `Sella(..., optimize_cell=True, hessian_function=)`), cached
-    and counted like the Hessian at fixed cell."""
+    and counted like the Hessian at fixed cell.  Its products without forming it are
+    cell_hessian_products(positions, cell, V (k, 3N + 9)) -> (k, 3N + 9) in the same coordinates, behind
+    cell_hessian_vector_product() (fits `Sella(..., optimize_cell=True, cell_hessian_vector_product=True)`); they are
+    neither force calls nor Hessians: `ncellhvps` counts the batches."""
 
     def __init__(self):
         self._key = None
@@ -271,6 +285,7 @@ class Calculator:
         self._hess = None                  # (cache key, DeviceMatrix, ndarray or None) of the last Hessian
         self._cell_hess = None             # the same of the last Hessian of positions and cell
         self.nhessians = 0                 # Hessians and batches of Hessian-vector products evaluated
+        self.ncellhvps = 0                 # batches of products with the Hessian of positions and cell
 
     def _library_calls(self):
         dc = getattr(self, '_devcalc', None)
@@ -303,8 +318,12 @@ class Calculator:
     def device_cell_hessian(self, pos, cell):
         raise NotImplementedError(f'{type(self).__name__} has no analytic Hessian of positions and cell')
 
+    def cell_hessian_products(self, pos, cell, V):
+        raise NotImplementedError(f'{type(self).__name__} has no Hessian-vector product of positions and cell')
+
     has_hessian = property(lambda self: type(self).device_hessian is not Calculator.device_hessian)
     has_cell_hessian = property(lambda self: type(self).device_cell_hessian is not Calculator.device_cell_hessian)
+    has_cell_hvp = property(lambda self: type(self).cell_hessian_products is not Calculator.cell_hessian_products)
 
     def _prepare(self, atoms):
         """Whatever depends on the species and the cell of `atoms` rather than on the positions (nothing here)."""
@@ -376,6 +395,21 @@ class Calculator:
             raise ValueError(f'expected vectors of length {n} as an array of shape ({n},) or (k, {n}), got {V.shape}')
         self.nhessians += 1
         return np.asarray(self.hessian_products(atoms.positions, V.reshape(-1, n))).reshape(V.shape)
+
+    def cell_hessian_vector_product(self, atoms, V):
+        """The Hessian of positions and cell times one vector (3N + 9,) or the rows of V (k, 3N + 9), each
+        [v; W.ravel()] in the coordinates of `get_cell_hessian` (W the variation of the cell, lattice vectors in its rows),
+        without forming it; the shape of V."""
+        if not self.has_cell_hvp:
+            raise NotImplementedError(f'{type(self).__name__} has no Hessian-vector product of positions and cell')
+        self._prepare(atoms)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        n = 3 * len(atoms) + 9
+        if V.shape != (n,) and (V.ndim != 2 or V.shape[1] != n or V.shape[0] == 0):
+            raise ValueError(f'expected vectors of length {n} as an array of shape ({n},) or (k, {n}), got {V.shape}')
+        self.ncellhvps += 1
+        cell = np.array(atoms.cell, dtype=np.float64)
+        return np.asarray(self.cell_hessian_products(atoms.positions, cell, V.reshape(-1, n))).reshape(V.shape)
 
     def _get(self, atoms, stress=False):
         """(E, dE/dx) of the geometry of `atoms`; with `stress`, the virial is cached alongside them from the same
@@ -534,7 +568,8 @@ class EMT(Calculator):
     get_stress() takes energy, forces and the virial from one device evaluation (`sella_emt_eval_stress`);
     get_hessian() / get_device_hessian() / hessian_vector_product() are the analytic second derivatives
     (`sella_emt_hessian`, `sella_emt_hvp`), get_cell_hessian() / get_device_cell_hessian() those of positions and cell
-    together (`sella_emt_cell_hessian`)."""
+    together (`sella_emt_cell_hessian`), cell_hessian_vector_product() their products without the matrix
+    (`sella_emt_cell_hvp`)."""
     #              E0     s0    V0     eta2   kappa  lambda n0        (eV, bohr, eV, 1/bohr, 1/bohr, 1/bohr, 1/bohr^3)
     _PAR = dict(Al=(-3.28, 3.00, 1.493, 1.240, 2.000, 1.169, 0.00700), Cu=(-3.51, 2.67, 2.476, 1.652, 2.740, 1.906, 0.00910),
                 Ag=(-2.96, 3.01, 2.132, 1.652, 2.790, 1.892, 0.00547), Au=(-3.80, 3.00, 2.321, 1.674, 2.873, 2.182, 0.00703),
@@ -639,6 +674,11 @@ class EMT(Calculator):
         from .device import get_context
         pos, par, shifts, *tail = self._emt_args(pos)
         return get_context().emt_cell_hessian(pos, par, shifts, cell, *tail)
+
+    def cell_hessian_products(self, pos, cell, V):
+        from .device import get_context
+        pos, par, shifts, *tail = self._emt_args(pos)
+        return get_context().emt_cell_hvp(pos, par, shifts, cell, *tail, V)
 
     library_form = True
 

@@ -42,6 +42,16 @@
 //   emt_hessian passes into the leading 3n x 3n block -> emt_cell_pair (per atom: the pair term of row block i of A, row i
 //   of gamma, atom i's share of B: 36 numbers, K_ab n_k n_l being symmetric in (a,b) and in (k,l)) -> emt_cell_embed (A +=
 //   (diag(F2) G^T)^T gamma) -> emt_cell_finish (B from the shares and gamma, summed in a fixed order; A^T into the last rows)
+//
+// The product with that Hessian (sella_emt_cell_hvp).  A direction [v; W] (W the 3 x 3 variation of C) displaces the pair
+// of a visit by dd = v_j - v_i + n_s W (for an own image: n_s W), and [A-part; B-part] applied to it is, with
+// c_i = g_i . v + gamma_i . W = sum_all visits of i  w'_ij u . dd,
+//     (y_x)_i      = - sum_visits of i, j != i  [ K dd + u (F2_i c_i w'_ij + F2_j c_j w'_ji) ]
+//     y_C[(k,b)]   = sum_i s_i[(k,b)],   s_i[(k,b)] = sum_all visits of i  n_k [ 1/2 (K dd)_b + F2_i c_i w'_ij u_b ]
+// (the 1/2 of B; the second term of s_i is F2_i c_i gamma_i): the two passes of the product at fixed cell with dd in place
+// of v_j - v_i and own images included, nine more sums per vector, and a sum over the atoms in a fixed order.
+//   emt_f2 -> emt_chvp_dots (c_i) -> emt_chvp_gather ((y_x)_i and s_i; the table T_q[s] = n_s W_q of every vector comes from
+//   the host) -> emt_chvp_finish (y_C), CHVP_KQ vectors per workgroup; nothing of size (3n)^2 is formed
 #include <cmath>
 #include <type_traits>
 
@@ -650,6 +660,147 @@ __device__ __forceinline__ void emt_cell_finish_vb(const VB vb, int n, EmtCell o
 }
 __global__ __launch_bounds__(256) void emt_cell_finish_kernel(int n, EmtCell o) { emt_cell_finish_vb(vb_hw(), n, o); }
 
+// ---- the product in the coordinates of the cell Hessian (sella_emt_cell_hvp) ------------------------------------------------
+// y = [A-part, B-part] applied to a direction [v; W] (W the 3 x 3 variation of C) without forming anything: the direction
+// displaces the pair of a visit by dd = v_j - v_i + n_s W, and with that in place of v_j - v_i the two passes of the
+// product at fixed cell give the position rows; the cell rows are the same pair quantities contracted with n_k (header).
+// T_q[s] = n_s W_q comes from the host (nshift x 3 per vector), so a visit costs one more 3-vector load per vector.  Twelve
+// accumulators per vector in the gather pass (three position components, nine cell entries) against three at fixed cell:
+// CHVP_KQ vectors per workgroup (profiles/cell_hvp.md).
+constexpr int CHVP_KQ = 4;
+
+struct EmtCellHvp {                         // k vectors: every array holds round_up(k, CHVP_KQ) rows, those of V and T beyond k zero
+    const double* F2;
+    const double* nimg;                     // nshift x 3: n_s
+    const double* T;                        // (k, nshift, 3): T_q[s] = n_s W_q
+    const double* V;                        // (k, ld): [v; W.ravel()]
+    double* HV;                             // (k, ld)
+    int ld;                                 // 3n + 9
+    double* cdot;                           // (k, n): c_i = sum_visits w'_ij u . dd
+    double* share;                          // (k, n, 9): atom i's share of the cell rows, column 3 k + b
+};
+
+// c_i[q] = g_i . v_q + gamma_i . W_q = sum over ALL visits of atom i (its own images too: dd = T_q[s] there) of w' u . dd
+__device__ __forceinline__ void emt_chvp_dots_vb(const VB vb, EmtArgs a, EmtCellHvp o) {
+    __shared__ double part[4][CHVP_KQ];
+    __shared__ int incomplete;
+    const int i = vb.x, q0 = vb.y * CHVP_KQ;
+    const EmtAtom m = emt_atom(a, i);
+    double vi[CHVP_KQ][3], acc[CHVP_KQ];
+#pragma unroll
+    for (int q = 0; q < CHVP_KQ; ++q) {
+        const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * i;
+        vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
+        acc[q] = 0.0;
+    }
+    auto visit = [&](int t) {
+        EmtPair p;
+        if (!emt_pair<true>(a, m, t, p)) return;
+        const int s = t >> 24;
+#pragma unroll
+        for (int q = 0; q < CHVP_KQ; ++q) {
+            const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * p.j;
+            const double* T = o.T + ((size_t)(q0 + q) * a.nshift + s) * 3;
+            const double dx = v[0] - vi[q][0] + T[0], dy = v[1] - vi[q][1] + T[1], dz = v[2] - vi[q][2] + T[2];
+            acc[q] += p.wp_ij * (p.ux * dx + p.uy * dy + p.uz * dz);
+        }
+    };
+    emt_by_image<false>(a, i, &incomplete, visit);
+#pragma unroll
+    for (int q = 0; q < CHVP_KQ; ++q) hvb_put<CHVP_KQ>(part, q, acc[q]);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < CHVP_KQ) o.cdot[(size_t)(q0 + t) * a.n + i] = hvb_total<CHVP_KQ>(part, t);
+}
+__global__ __launch_bounds__(256) void emt_chvp_dots_kernel(EmtArgs a, EmtCellHvp o) { emt_chvp_dots_vb(vb_hw(), a, o); }
+
+// position rows: (y_x)_i = - sum over the visits with j != i of [K dd + u (F2_i c_i w'_ij + F2_j c_j w'_ji)]
+// cell rows, atom i's share: s_i[(k, b)] = sum over ALL visits of n_k [1/2 (K dd)_b + F2_i c_i w'_ij u_b] (the 1/2 of the
+// `B` formula; the second term is F2_i c_i gamma_i).  The twelve sums of a vector are reduced behind one barrier.
+__device__ __forceinline__ void emt_chvp_gather_vb(const VB vb, EmtArgs a, EmtCellHvp o) {
+    constexpr int NS = 12 * CHVP_KQ;
+    __shared__ double part[4][NS];
+    __shared__ int incomplete;
+    const int i = vb.x, q0 = vb.y * CHVP_KQ;
+    const EmtAtom m = emt_atom(a, i);
+    const double f2i = o.F2[i];
+    double vi[CHVP_KQ][3], fc[CHVP_KQ], ax[CHVP_KQ][3], ac[CHVP_KQ][9];
+#pragma unroll
+    for (int q = 0; q < CHVP_KQ; ++q) {
+        const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * i;
+        vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
+        fc[q] = f2i * o.cdot[(size_t)(q0 + q) * a.n + i];
+        ax[q][0] = ax[q][1] = ax[q][2] = 0.0;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) ac[q][c] = 0.0;
+    }
+    auto visit = [&](int t) {
+        EmtPair p;
+        if (!emt_pair<true>(a, m, t, p)) return;
+        const int s = t >> 24;
+        const double* ns = o.nimg + 3 * s;
+        const double nv[3] = {ns[0], ns[1], ns[2]};
+        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
+        const double f2j = o.F2[p.j];
+        const double other = p.j != i ? 1.0 : 0.0;                                // an own image moves no position block
+#pragma unroll
+        for (int q = 0; q < CHVP_KQ; ++q) {
+            const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * p.j;
+            const double* T = o.T + ((size_t)(q0 + q) * a.nshift + s) * 3;
+            const double dx = v[0] - vi[q][0] + T[0], dy = v[1] - vi[q][1] + T[1], dz = v[2] - vi[q][2] + T[2];
+            const double along = c2 * (p.ux * dx + p.uy * dy + p.uz * dz);
+            const double kd[3] = {c1 * dx + along * p.ux, c1 * dy + along * p.uy, c1 * dz + along * p.uz};   // K dd
+            const double own = fc[q] * p.wp_ij;
+            const double emb = other * (own + f2j * o.cdot[(size_t)(q0 + q) * a.n + p.j] * p.wp_ji);
+            const double u[3] = {p.ux, p.uy, p.uz};
+#pragma unroll
+            for (int b = 0; b < 3; ++b) {
+                ax[q][b] -= other * kd[b] + emb * u[b];
+                const double tb = 0.5 * kd[b] + own * u[b];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) ac[q][3 * k + b] += nv[k] * tb;
+            }
+        }
+    };
+    emt_by_image<false>(a, i, &incomplete, visit);
+#pragma unroll
+    for (int q = 0; q < CHVP_KQ; ++q) {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) hvb_put<NS>(part, 12 * q + b, ax[q][b]);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) hvb_put<NS>(part, 12 * q + 3 + c, ac[q][c]);
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= NS) return;
+    const int q = q0 + t / 12, c = t % 12;
+    const double v = hvb_total<NS>(part, t);
+    if (c < 3) o.HV[(size_t)q * o.ld + 3 * i + c] = v;
+    else o.share[((size_t)q * a.n + i) * 9 + (c - 3)] = v;
+}
+__global__ __launch_bounds__(256) void emt_chvp_gather_kernel(EmtArgs a, EmtCellHvp o) { emt_chvp_gather_vb(vb_hw(), a, o); }
+
+// cell rows of vector vb.x: y_C = sum_i s_i — every thread adds its atoms (i = tid, tid + 256, ...) in increasing i, then
+// block_sum's arithmetic over the threads: one fixed order
+__device__ __forceinline__ void emt_chvp_finish_vb(const VB vb, int n, EmtCellHvp o) {
+    __shared__ double part[4][9];
+    const int q = vb.x;
+    double acc[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) acc[c] = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double* s = o.share + ((size_t)q * n + i) * 9;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) acc[c] += s[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) hvb_put<9>(part, c, acc[c]);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < 9) o.HV[(size_t)q * o.ld + 3 * n + t] = hvb_total<9>(part, t);
+}
+__global__ __launch_bounds__(256) void emt_chvp_finish_kernel(int n, EmtCellHvp o) { emt_chvp_finish_vb(vb_hw(), n, o); }
+
 struct TempMats {                           // device matrices of one call, back to the pool on every way out (stream-ordered)
     sella_ctx* c;
     sella_mat h[3] = {SELLA_NO_MAT, SELLA_NO_MAT, SELLA_NO_MAT};
@@ -767,6 +918,49 @@ extern "C" int sella_emt_cell_hessian(sella_ctx* c, int n, const double* pos, co
                   (const double*)Gs->d, Gs->ld, o);
     SELLA_LAUNCHB(c, emt_cell_finish_kernel, emt_cell_finish_vb, 256, dim3(45 + (n3 + 255) / 256), dim3(256), 0, n, o);
     HIPCHK(hipGetLastError());
+    return stream_wait(c);
+}
+
+// V, HV: (k, 3n + 9) host arrays, one vector [v; W.ravel()] per row, in the coordinates of sella_emt_cell_hessian
+extern "C" int sella_emt_cell_hvp(sella_ctx* c, int n, const double* pos, const double* par /* 9 x n */, int nshift,
+                                  const double* shifts, const double* cell, double rc, double acut, double cutoff, double beta,
+                                  const double* V, int k, double* HV) {
+    if (!c || n <= 0 || !pos || !par || nshift <= 0 || !shifts || !cell || !V || k <= 0 || !HV) {
+        set_error("emt_cell_hvp: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    if (nshift > 127) { set_error("emt: at most 2^24 atoms and 127 periodic images"); return SELLA_E_INVALID; }
+    std::vector<double> nimg;
+    SCHK(emt_image_indices(cell, nshift, shifts, nimg));
+    const size_t dim = (size_t)3 * n + 9, kp = (size_t)round_up(k, CHVP_KQ), nT = (size_t)3 * nshift;
+    std::vector<double> T(kp * nT, 0.0);                              // T_q[s] = n_s W_q; zero for the rows beyond k
+    for (int q = 0; q < k; ++q) {
+        const double* W = V + (size_t)q * dim + (size_t)3 * n;
+        for (int s = 0; s < nshift; ++s)
+            for (int b = 0; b < 3; ++b)
+                T[(size_t)q * nT + 3 * s + b] = nimg[3 * s] * W[b] + nimg[3 * s + 1] * W[3 + b] + nimg[3 * s + 2] * W[6 + b];
+    }
+    EmtArgs a;
+    double* ex;                     // F2 (n), image indices (3 nshift), T (kp 3 nshift), V and HV (kp dim each), dots (kp n), shares (kp 9 n)
+    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta,
+                           (size_t)n + nT + kp * (nT + 2 * dim + (size_t)10 * n), &a, &ex));
+    double* dn = ex + n;
+    double* dT = dn + nT;
+    double* dV = dT + kp * nT;
+    EmtCellHvp o;
+    o.F2 = ex; o.nimg = dn; o.T = dT; o.V = dV; o.HV = dV + kp * dim; o.ld = (int)dim;
+    o.cdot = o.HV + kp * dim; o.share = o.cdot + kp * n;
+    SCHK(h2d_async(c, dn, nimg.data(), nT * sizeof(double)));
+    SCHK(h2d_async(c, dT, T.data(), kp * nT * sizeof(double)));
+    SCHK(h2d_async(c, dV, V, (size_t)k * dim * sizeof(double)));
+    if (kp > (size_t)k) HIPCHK(s_memset0(c, dV + (size_t)k * dim, (kp - k) * dim * sizeof(double)));
+    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, ex);
+    const dim3 grid(n, (unsigned)(kp / CHVP_KQ));
+    SELLA_LAUNCHB(c, emt_chvp_dots_kernel, emt_chvp_dots_vb, 256, grid, dim3(256), 0, a, o);
+    SELLA_LAUNCHB(c, emt_chvp_gather_kernel, emt_chvp_gather_vb, 256, grid, dim3(256), 0, a, o);
+    SELLA_LAUNCHB(c, emt_chvp_finish_kernel, emt_chvp_finish_vb, 256, dim3(k), dim3(256), 0, n, o);
+    HIPCHK(hipGetLastError());
+    SCHK(d2h_async(c, HV, o.HV, (size_t)k * dim * sizeof(double)));
     return stream_wait(c);
 }
 

@@ -696,6 +696,21 @@ class Context:
                                        float(acut), float(cutoff), float(beta), ptr(V), V.shape[0], ptr(HV)))
         return HV.reshape(shape)
 
+    def emt_cell_hvp(self, pos, par, shifts, cell, rc, acut, cutoff, beta, V):
+        """The Hessian of positions and cell times the rows of V (k, 3n + 9) (or one vector (3n + 9,)), each
+        [v; W.ravel()] in the coordinates of `emt_cell_hessian`, without forming it (`sella_emt_cell_hvp`); same shape
+        as V."""
+        pos = as_f64(pos)
+        par = as_f64(par)
+        shifts = as_f64(shifts)
+        cell = as_f64(cell, (3, 3))
+        n = pos.shape[0]
+        V, shape = _hvp_vectors(V, 3 * n + 9)
+        HV = np.empty_like(V)
+        check(_lib.lib().sella_emt_cell_hvp(self._h, n, ptr(pos), ptr(par), shifts.shape[0], ptr(shifts), ptr(cell),
+                                            float(rc), float(acut), float(cutoff), float(beta), ptr(V), V.shape[0], ptr(HV)))
+        return HV.reshape(shape)
+
     # ---- profiling ---------------------------------------------------------------------------
     def prof_enable(self, on=True):
         check(_lib.lib().sella_prof_enable(self._h, int(bool(on))))

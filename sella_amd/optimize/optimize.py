@@ -47,7 +47,7 @@ class Sella(Optimizer):
                  hessian_function=None, optimize_cell=False, cell_mask=None, exp_cell_factor=None,
                  scalar_pressure=0.0, smax=None, allow_fragments=False, niggli=False,
                  refine_initial_hessian=False, save_hessian=None, exact_geodesic=None, hessian_vector_product=None,
-                 **kwargs):
+                 cell_hessian_vector_product=None, **kwargs):
         # keyword set of the reference constructor (optimize.py:42-80).  The cell keywords (cell_mask,
         # exp_cell_factor, scalar_pressure, smax, niggli, refine_initial_hessian, save_hessian) only act with
         # optimize_cell=True, there as here.
@@ -61,8 +61,19 @@ class Sella(Optimizer):
                 raise ValueError('hessian_function and hessian_vector_product are two sources of curvature: give one')
             if internal or optimize_cell:
                 raise NotImplementedError('hessian_vector_product is implemented for Cartesian coordinates at fixed cell only '
-                                          '(not with internal=True or optimize_cell=True)')
+                                          '(not with internal=True or optimize_cell=True; a cell run takes '
+                                          'cell_hessian_vector_product=)')
             kwargs = dict(kwargs, hessian_vector_product=hessian_vector_product)
+        # cell_hessian_vector_product (True: the calculator's own; or f(atoms, V (k, 3N + 9)) -> (k, 3N + 9) in the
+        # coordinates [positions; cell.ravel()]): the same for a cell run — a keyword of its own, as a cell run takes the
+        # (3N + 9)-square `hessian_function` and refuses the 3N x 3N one
+        if cell_hessian_vector_product is False:
+            cell_hessian_vector_product = None
+        if cell_hessian_vector_product is not None:
+            if not optimize_cell:
+                raise ValueError('cell_hessian_vector_product needs optimize_cell=True (at fixed cell: hessian_vector_product=)')
+            if hessian_function is not None:
+                raise ValueError('hessian_function and cell_hessian_vector_product are two sources of curvature: give one')
         if optimize_cell:
             self._check_cell_run(atoms, order, internal, niggli)
         self.optimize_cell = bool(optimize_cell)
@@ -70,6 +81,8 @@ class Sella(Optimizer):
         self.delta_cell = None
         cell_kw = dict(cell_mask=cell_mask, exp_cell_factor=exp_cell_factor, scalar_pressure=scalar_pressure,
                        refine_initial_hessian=refine_initial_hessian, save_hessian=save_hessian)
+        if cell_hessian_vector_product is not None:
+            cell_kw['cell_hessian_vector_product'] = cell_hessian_vector_product
         # allow_fragments: disconnected fragments get TRIC translations and rotations instead of artificial bonds
         # between them (internal coordinates only; accepted and ignored in Cartesian coordinates, as the reference)
         self.allow_fragments = bool(allow_fragments)

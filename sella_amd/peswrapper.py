@@ -107,6 +107,7 @@ class PES:
     # `hessian_vector_product=`: exact products for the iterative diagonalisation, Cartesian coordinates only (the
     # subclasses for internal coordinates and for the cell refuse the keyword)
     _accepts_hvp = True
+    _hvp_hint = ''
 
     def __init__(self, atoms, H0=None, constraints=None, eigensolver='jd0', trajectory=None,
                  eta=1e-4, v0=None, proj_trans=None, proj_rot=None, hessian_function=None, hessian_vector_product=None):
@@ -136,7 +137,7 @@ class PES:
             return None
         if not self._accepts_hvp:
             raise NotImplementedError(f'hessian_vector_product is not implemented for {type(self).__name__}: the products '
-                                      f'exist in Cartesian coordinates at fixed cell only')
+                                      f'exist in Cartesian coordinates at fixed cell only{self._hvp_hint}')
         if hvp is True:
             from .atoms import supports_hessian
             calc = getattr(atoms, 'calc', None)
@@ -431,7 +432,7 @@ class PES:
             # exact products (`hessian_vector_product=`): no displacement, so `threepoint` has no meaning here
             Hproj = self._library_hvp_operator(Ufree)
             if Hproj is None:
-                Hproj = AnalyticHessian(self._hvp, self.ncart, Ufree)
+                Hproj = AnalyticHessian(self._hvp, self.dim, Ufree)
         else:
             Hproj = self._library_fd_operator(Ufree, threepoint)
             if Hproj is None:
@@ -1180,14 +1181,21 @@ class CellCartesianPES(PES):
     evaluations, step hessian_delta; not run with a hessian_function); save_hessian names an .npy file for it.
     hessian_function(atoms) returns the (3N + 9)-square Hessian in the coordinates [positions; cell.ravel()] (lattice
     vectors in the rows of the cell, positions fixed while the cell varies), as an array or a `DeviceMatrix`, e.g.
-    `EMT.get_device_cell_hessian`; `calculate_hessian` carries it into the PES's own coordinates."""
+    `EMT.get_device_cell_hessian`; `calculate_hessian` carries it into the PES's own coordinates.
+    cell_hessian_vector_product (True: the calculator's own, e.g. `EMT.cell_hessian_vector_product`; or a callable
+    f(atoms, V (k, 3N + 9)) -> (k, 3N + 9) in the same coordinates) gives the iterative diagonalisation exact products
+    instead of finite differences of the gradient: `diag` carries every vector into [x; C.ravel()] and the product back
+    (`_cell_hvp`), without a force call.  `hessian_vector_product=` (products of 3N) stays refused, like a 3N x 3N
+    `hessian_function`."""
     _accepts_hvp = False
+    _hvp_hint = ' (a cell run takes cell_hessian_vector_product=)'
 
     def __init__(self, atoms, H0=None, constraints=None, eigensolver='jd0', trajectory=None, eta=1e-4, v0=None,
                  proj_trans=None, proj_rot=None, hessian_function=None, exp_cell_factor=None, cell_mask=None,
                  scalar_pressure=0.0, refine_initial_hessian=False, hessian_delta=1e-5, save_hessian=None,
-                 hessian_vector_product=None):
-        self._resolve_hvp(atoms, hessian_vector_product)            # (refused: no products in the cell coordinates)
+                 hessian_vector_product=None, cell_hessian_vector_product=None):
+        self._resolve_hvp(atoms, hessian_vector_product)            # (refused: products of 3N say nothing about the cell)
+        cell_hvp = self._resolve_cell_hvp(atoms, cell_hessian_vector_product)
         self.orig_cell = np.array(atoms.get_cell(), dtype=np.float64)
         self.exp_cell_factor = float(len(atoms)) if exp_cell_factor is None else float(exp_cell_factor)
         mask = np.ones((3, 3), dtype=bool) if cell_mask is None else np.asarray(cell_mask, dtype=bool).reshape((3, 3))
@@ -1198,6 +1206,9 @@ class CellCartesianPES(PES):
                      eta=eta, v0=v0, proj_trans=proj_trans, proj_rot=proj_rot, hessian_function=hessian_function)
         nc = self.ncart
         self.dim = nc + self.n_cell_dof
+        self._cell_hvp_source, self._cell_maps_cache = cell_hvp, _LRU2()
+        if cell_hvp is not None:
+            self._hvp = self._cell_hvp                           # what `PES.diag` takes its products from
         if H0 is not None:
             H0 = np.asarray(H0, dtype=np.float64)
             if H0.shape == (nc, nc):                             # positions only: the cell block as by default
@@ -1327,28 +1338,82 @@ class CellCartesianPES(PES):
                     D1[i] = X[0:3, 3:6]
         return D1, half + half.transpose(1, 0, 2, 3)
 
-    def _cell_block_to_params(self, rows):
-        """The cell rows of the Hessian in the PES's own coordinates, (m, 3N + m), from the nine cell rows `rows`
-        (9, 3N + 9) of the Hessian in [x; C.ravel()].  With U = L / exp_cell_factor, C = expm(U) C0 and the masked unit
-        directions E_m: J[:, m] = vec(D expm(U)[E_m] C0) / exp_cell_factor, H_px = J^T H_Cx, and
-        H_pp = J^T H_CC J + sum_ab dEdC_ab (D2 expm(U)[E_m, E_q] C0)_ab / exp_cell_factor^2; p V adds
-        p d2|det C|/dC2 to H_CC first (its first derivative is part of dEdC)."""
-        nc, fac = self.ncart, self.exp_cell_factor
+    def _cell_param_maps(self):
+        """(J (9, m), G0 (m, m), P (9, 9) or None) of the current geometry, what carries second derivatives from
+        [x; C.ravel()] into the PES's coordinates: with U = L / exp_cell_factor, C = expm(U) C0 and the masked unit
+        directions E_m, J[:, m] = vec(D expm(U)[E_m] C0) / exp_cell_factor, G0[m, q] = sum_ab dEdC_ab
+        (D2 expm(U)[E_m, E_q] C0)_ab / exp_cell_factor^2 (symmetric up to rounding), and P = p d2|det C|/dC2, which p V adds
+        to H_CC (its first derivative is part of dEdC).  Computed once per geometry (m^2 9 x 9 exponentials): the dense
+        conversion and every product of `_cell_hvp` share them."""
+        key = (self._state_hash(), self.orig_cell.tobytes())             # (`load_state` replaces the reference cell)
+        hit = self._cell_maps_cache.get(key)
+        if hit is not None:
+            return hit
+        fac = self.exp_cell_factor
         stress = np.asarray(self.atoms.get_stress(), dtype=np.float64)
         forces = np.asarray(self.atoms.get_forces(), dtype=np.float64).reshape((-1, 3))
         dEdC, C = self._dEdC(stress, forces)
-        H_Cx, H_CC = rows[:, :nc], rows[:, nc:].copy()
+        P = None
         if self.scalar_pressure != 0.0:
             Ci = np.linalg.inv(C)
             # d2 det C / dC_ab dC_cd = det C (C^-1_ba C^-1_dc - C^-1_da C^-1_bc)
             d2 = np.einsum('ba,dc->abcd', Ci, Ci) - np.einsum('da,bc->abcd', Ci, Ci)
-            H_CC += self.scalar_pressure * abs(np.linalg.det(C)) * d2.reshape(9, 9)
+            P = self.scalar_pressure * abs(np.linalg.det(C)) * d2.reshape(9, 9)
         U = logm_3x3(C @ np.linalg.inv(self.orig_cell))
         D1, D2 = self._expm_derivatives(U)
         J = (D1 @ self.orig_cell).reshape(len(D1), 9).T / fac             # (9, m)
         dEdF = dEdC @ self.orig_cell.T
-        H_pp = J.T @ H_CC @ J + np.einsum('ab,mqab->mq', dEdF, D2) / fac ** 2
+        G0 = np.einsum('ab,mqab->mq', dEdF, D2) / fac ** 2
+        out = (J, G0, P)
+        self._cell_maps_cache.put(key, out)
+        return out
+
+    def _cell_block_to_params(self, rows):
+        """The cell rows of the Hessian in the PES's own coordinates, (m, 3N + m), from the nine cell rows `rows`
+        (9, 3N + 9) of the Hessian in [x; C.ravel()], with J, G0 and P of `_cell_param_maps`: H_px = J^T H_Cx and
+        H_pp = J^T (H_CC + P) J + G0, symmetrised."""
+        nc = self.ncart
+        J, G0, P = self._cell_param_maps()
+        H_Cx, H_CC = rows[:, :nc], rows[:, nc:].copy()
+        if P is not None:
+            H_CC += P
+        H_pp = J.T @ H_CC @ J + G0
         return np.hstack([J.T @ H_Cx, 0.5 * (H_pp + H_pp.T)])
+
+    # ---- exact products: cell_hessian_vector_product in the coordinates [x; C.ravel()] -----------------------------------
+    def _resolve_cell_hvp(self, atoms, hvp):
+        """`f(atoms, V (k, 3N + 9)) -> (k, 3N + 9)` from the keyword `cell_hessian_vector_product`: True takes the
+        calculator's own, a callable is taken as it is."""
+        if hvp is None or hvp is False:
+            return None
+        if hvp is True:
+            from .atoms import supports_cell_hvp
+            calc = getattr(atoms, 'calc', None)
+            if not supports_cell_hvp(calc):
+                raise NotImplementedError(f'cell_hessian_vector_product=True needs a calculator with its own Hessian-vector '
+                                          f'product of positions and cell, and {type(calc).__name__} has none')
+            return calc.cell_hessian_vector_product
+        if not callable(hvp):
+            raise TypeError('cell_hessian_vector_product must be True or a callable f(atoms, V (k, 3N + 9)) -> (k, 3N + 9)')
+        return hvp
+
+    def _cell_hvp(self, V):
+        """H V[q] for the rows [v_x; v_p] of V (k, dim) in the PES's own coordinates: W = J v_p is the variation of the
+        cell, [y_x; y_C] the product in [x; C.ravel()] (p V adds P W to y_C), and y_p = J^T y_C + G v_p with
+        G = (G0 + G0^T) / 2 — row by row what `_convert_cell_hessian` does to the matrix."""
+        nc = self.ncart
+        V = np.asarray(V, dtype=np.float64).reshape(-1, self.dim)
+        J, G0, P = self._cell_param_maps()
+        Vp = V[:, nc:]
+        W = Vp @ J.T                                                       # (k, 9)
+        Y = np.asarray(self._cell_hvp_source(self.atoms, np.hstack([V[:, :nc], W])), dtype=np.float64)
+        if Y.shape != (V.shape[0], nc + 9):
+            raise ValueError(f'cell_hessian_vector_product must return {V.shape[0]} x {nc + 9} products of the '
+                             f'{len(self.atoms)} atoms and the nine cell entries, got {" x ".join(str(k) for k in Y.shape)}')
+        yC = Y[:, nc:]
+        if P is not None:
+            yC = yC + W @ P.T
+        return np.hstack([Y[:, :nc], yC @ J + Vp @ (0.5 * (G0 + G0.T)).T])
 
     def _convert_cell_hessian(self, H, consume=False):
         """The Hessian in the PES's coordinates [x; p] of what a `hessian_function` returns in a cell run: the
