@@ -31,7 +31,19 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
     return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-constexpr int EMT_HCAP = 8;                // slots of a thread's neighbour list
+// block_sum's arithmetic for NS sums behind ONE barrier: every thread puts its share of each sum, the wavefronts' sums lie
+// side by side in LDS (part[4][NS]), and after a __syncthreads() any thread reads sum `slot` with block_total
+template <int NS>
+__device__ __forceinline__ void block_put(double (*part)[NS], int slot, double v) {
+    v = wave_sum64(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][slot] = v;
+}
+template <int NS>
+__device__ __forceinline__ double block_total(const double (*part)[NS], int slot) {
+    return (part[0][slot] + part[1][slot]) + (part[2][slot] + part[3][slot]);
+}
+
+constexpr int EMT_HCAP = 8;               // slots of a thread's neighbour list
 
 // a noted pair: atom index in the low 24 bits, image above (no division when it is taken up again)
 __device__ __forceinline__ int emt_pack(int j, int s) { return (s << 24) | j; }

@@ -15,18 +15,22 @@
 // density pass and takes both ordered pairs (i <- j) and (j <- i) of a visit together (same distance).
 //   dense:   emt_f2 (per atom) -> emt_hess_pair (row block i of H: -K off the diagonal, sum K on it; row i of G^T and of
 //            diag(F2) G^T) -> H += G diag(F2) G^T on the matrix cores (launch_gemm) -> (H + H^T) / 2
-//   product: emt_f2 -> emt_hvp_dots (c_i = g_i . v) -> emt_hvp_gather ((H v)_i from c_i, c_j and the pair blocks), for up
-//            to HVP_KQ vectors per workgroup
-//   operator: the same two product kernels for ONE vector (emt_hvp1_dots, emt_hvp1_gather: 3 accumulators per thread instead
-//            of 24) on a state that is built once per geometry and owned by the operator (EmtHvpState: positions, sigma1,
-//            dEdsig, the lists, F2), device vector in, device vector out, nothing waited for (calc.hip, sella_hvp_*)
-//   block:   the product for the up to 16 rows of a device panel on the same state (emt_hvpb_dots, emt_hvpb_gather: all 16
-//            vectors in one workgroup per atom; the free rows written straight into the caller's panel), and the diagonal
-//            of H (emt_hdiag) — the operator of the block Davidson
+//   product: emt_f2 -> dots (c_i = g_i . v) -> gather ((H v)_i from c_i, c_j and the pair blocks).  The two passes are
+//            written once (emt_dots_body, emt_gather_body) over a description of the vectors a workgroup carries; the
+//            kernels are its instantiations:
+//              emt_hvp_dots, emt_hvp_gather     HVP_KQ rows of host vectors per workgroup
+//              emt_hvp1_dots, emt_hvp1_gather   the operator: ONE vector (3 accumulators per thread instead of 24) on a state
+//                    that is built once per geometry and owned by the operator (EmtHvpState: positions, sigma1, dEdsig, the
+//                    lists, F2), device vector in, device vector out, nothing waited for (calc.hip, sella_hvp_*)
+//              emt_hvpb_dots, emt_hvpb_gather   the up to 16 rows of a device panel on the same state, all in one workgroup
+//                    per atom, the free rows written straight into the caller's panel — with the diagonal of H (emt_hdiag)
+//                    the operator of the block Davidson
+//              emt_chvp_dots, emt_chvp_gather   CHVP_KQ rows of positions and cell (below)
 // No atomics: an atom can be a neighbour through several images, and those visits belong to different threads unless
 // 256 divides N, so everything that lands in a shared place is added image by image with a barrier in between (one
 // writer per (i, j) within an image, images in index order); per-thread sums run in the order of the lists and are
-// reduced by block_sum.  The result does not depend on whether the lists were complete.
+// reduced with block_sum's arithmetic, all sums of a kernel behind one barrier (block_put, block_total: emt.h).  The
+// result does not depend on whether the lists were complete.
 //
 // The cell (sella_emt_cell_hessian).  The lattice vectors (rows of C) enter only through the image translations
 // S_s = n_s C, n_s whole numbers: for a visit d = x_j + n_s C - x_i, so dd_a / dC_kb = n_k delta_ab, and in the coordinates
@@ -161,6 +165,16 @@ __device__ __forceinline__ void emt_by_image(const EmtArgs& a, int i, int* incom
     }
 }
 
+// symmetric index of (a, b), a, b in 0..2, in the order xx, yy, zz, yz, xz, xy
+__host__ __device__ __forceinline__ int sym6(int a, int b) { return a == b ? a : 6 - a - b; }
+
+// K = c1 I + c2 u u^T of a visit, in the order of sym6
+__device__ __forceinline__ void emt_pair_K(const EmtPair& p, double K[6]) {
+    const double c1 = p.e1 / p.r, c2 = p.e2 - c1;
+    K[0] = c1 + c2 * (p.ux * p.ux); K[1] = c1 + c2 * (p.uy * p.uy); K[2] = c1 + c2 * (p.uz * p.uz);
+    K[3] = c2 * (p.uy * p.uz); K[4] = c2 * (p.ux * p.uz); K[5] = c2 * (p.ux * p.uy);
+}
+
 struct EmtHessOut {
     const double* F2;
     double* H; int ldh;                     // 3n x 3n, zero on entry
@@ -169,7 +183,7 @@ struct EmtHessOut {
 
 // Row block i of the pair term of H, and rows i of G^T and diag(F2) G^T.
 __device__ __forceinline__ void emt_hess_pair_vb(const VB vb, EmtArgs a, EmtHessOut o) {
-    __shared__ double red[4];
+    __shared__ double part[4][9];
     __shared__ int incomplete;
     const int i = vb.x;
     const EmtAtom m = emt_atom(a, i);
@@ -177,33 +191,37 @@ __device__ __forceinline__ void emt_hess_pair_vb(const VB vb, EmtArgs a, EmtHess
     double* H1 = H0 + o.ldh;
     double* H2 = H1 + o.ldh;
     double* G = o.Gt + (size_t)i * o.ldg;
-    double kxx = 0.0, kyy = 0.0, kzz = 0.0, kyz = 0.0, kxz = 0.0, kxy = 0.0;       // diagonal block: sum of K
+    double kd[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};                                // diagonal block: sum of K
     double gx = 0.0, gy = 0.0, gz = 0.0;                                          // g_i on atom i: -sum w' u
     auto visit = [&](int t) {
         EmtPair p;
         if (!emt_pair(a, m, t, p)) return;
-        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
-        const double xx = c1 + c2 * (p.ux * p.ux), yy = c1 + c2 * (p.uy * p.uy), zz = c1 + c2 * (p.uz * p.uz);
-        const double yz = c2 * (p.uy * p.uz), xz = c2 * (p.ux * p.uz), xy = c2 * (p.ux * p.uy);
+        double K[6];
+        emt_pair_K(p, K);
         const int q = 3 * p.j;
-        H0[q] -= xx; H0[q + 1] -= xy; H0[q + 2] -= xz;
-        H1[q] -= xy; H1[q + 1] -= yy; H1[q + 2] -= yz;
-        H2[q] -= xz; H2[q + 1] -= yz; H2[q + 2] -= zz;
-        kxx += xx; kyy += yy; kzz += zz; kyz += yz; kxz += xz; kxy += xy;
+        H0[q] -= K[0]; H0[q + 1] -= K[5]; H0[q + 2] -= K[4];
+        H1[q] -= K[5]; H1[q + 1] -= K[1]; H1[q + 2] -= K[3];
+        H2[q] -= K[4]; H2[q + 1] -= K[3]; H2[q + 2] -= K[2];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) kd[c] += K[c];
         const double wx = p.wp_ij * p.ux, wy = p.wp_ij * p.uy, wz = p.wp_ij * p.uz;
         G[q] += wx; G[q + 1] += wy; G[q + 2] += wz;
         gx -= wx; gy -= wy; gz -= wz;
     };
     emt_by_image<true>(a, i, &incomplete, visit);
-    kxx = block_sum(kxx, red); kyy = block_sum(kyy, red); kzz = block_sum(kzz, red);
-    kyz = block_sum(kyz, red); kxz = block_sum(kxz, red); kxy = block_sum(kxy, red);
-    gx = block_sum(gx, red); gy = block_sum(gy, red); gz = block_sum(gz, red);
+#pragma unroll
+    for (int c = 0; c < 6; ++c) block_put<9>(part, c, kd[c]);
+    block_put<9>(part, 6, gx); block_put<9>(part, 7, gy); block_put<9>(part, 8, gz);
+    __syncthreads();
     if (threadIdx.x == 0) {
+        double s[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) s[c] = block_total<9>(part, c);
         const int q = 3 * i;
-        H0[q] = kxx; H0[q + 1] = kxy; H0[q + 2] = kxz;
-        H1[q] = kxy; H1[q + 1] = kyy; H1[q + 2] = kyz;
-        H2[q] = kxz; H2[q + 1] = kyz; H2[q + 2] = kzz;
-        G[q] = gx; G[q + 1] = gy; G[q + 2] = gz;
+        H0[q] = s[0]; H0[q + 1] = s[5]; H0[q + 2] = s[4];
+        H1[q] = s[5]; H1[q + 1] = s[1]; H1[q + 2] = s[3];
+        H2[q] = s[4]; H2[q + 1] = s[3]; H2[q + 2] = s[2];
+        G[q] = s[6]; G[q + 1] = s[7]; G[q + 2] = s[8];
     }
     __syncthreads();
     const double f2 = o.F2[i];
@@ -212,97 +230,193 @@ __device__ __forceinline__ void emt_hess_pair_vb(const VB vb, EmtArgs a, EmtHess
 }
 __global__ __launch_bounds__(256) void emt_hess_pair_kernel(EmtArgs a, EmtHessOut o) { emt_hess_pair_vb(vb_hw(), a, o); }
 
-struct EmtHvp {                             // k vectors: every array holds round_up(k, HVP_KQ) rows, those of V beyond k zero
+// ---- the two passes of a product ------------------------------------------------------------------------------------------
+// One workgroup per atom i carries W vectors through both passes: the pair quantities of a visit are evaluated once for
+// all of them.  What a kernel family chooses is a description P of its vectors:
+//   P::W                    how many vectors (accumulators per thread: W in the dots pass, 3 W or 12 W in the gather pass)
+//   P::CELL                 vectors [v; W] of positions and cell: an atom's own images are visits too, and the pair of a visit
+//                           through image s is displaced by shift(q, s) = T_q[s] = n_s W_q more; nimg = the n_s
+//   load(q, j, x)           x = row of atom j in vector q
+//   c(q, j)                 where the dot c_j of vector q lives
+//   P::Terms                the arithmetic of one vector in one visit, contracted or not (below)
+// The arithmetic of one vector in a visit, d the displacement of the pair by the vector.  It stands twice because `#pragma
+// clang fp contract` is lexical and no template can switch it: EmtTerms leaves the contraction into fused multiply-adds to
+// the compiler, EmtTermsExact rounds every product on its own (the panel of the block product: see there).
+struct EmtTerms {
+    static __device__ __forceinline__ double dot(const EmtPair& p, const double d[3]) {                  // w'_ij u . d
+        return p.wp_ij * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]);
+    }
+    // acc += K d - u (fi w'_ij + fj w'_ji), K = c1 I + c2 u u^T
+    static __device__ __forceinline__ void row(const EmtPair& p, double c1, double c2, const double d[3], double fi, double fj,
+                                               double acc[3]) {
+        const double along = c2 * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]) - (fi * p.wp_ij + fj * p.wp_ji);
+        acc[0] += c1 * d[0] + along * p.ux;
+        acc[1] += c1 * d[1] + along * p.uy;
+        acc[2] += c1 * d[2] + along * p.uz;
+    }
+};
+struct EmtTermsExact {
+    static __device__ __forceinline__ double dot(const EmtPair& p, const double d[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        return p.wp_ij * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]);
+    }
+    static __device__ __forceinline__ void row(const EmtPair& p, double c1, double c2, const double d[3], double fi, double fj,
+                                               double acc[3]) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        const double along = c2 * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]) - (fi * p.wp_ij + fj * p.wp_ji);
+        acc[0] += c1 * d[0] + along * p.ux;
+        acc[1] += c1 * d[1] + along * p.uy;
+        acc[2] += c1 * d[2] + along * p.uz;
+    }
+};
+
+// c_i[q] = sum over the visits of w'_ij u . dd, dd = v_j - v_i (+ T_q[s]): g_i . v_q (+ gamma_i . W_q; for an own image
+// dd = T_q[s])
+template <class P>
+__device__ __forceinline__ void emt_dots_body(const VB vb, const EmtArgs& a, const P& o) {
+    __shared__ double part[4][P::W];
+    __shared__ int incomplete;
+    const int i = vb.x;
+    const EmtAtom m = emt_atom(a, i);
+    double vi[P::W][3], acc[P::W];
+#pragma unroll
+    for (int q = 0; q < P::W; ++q) {
+        o.load(q, i, vi[q]);
+        acc[q] = 0.0;
+    }
+    auto visit = [&](int t) {
+        EmtPair p;
+        if (!emt_pair<P::CELL>(a, m, t, p)) return;
+#pragma unroll
+        for (int q = 0; q < P::W; ++q) {
+            double d[3];
+            o.load(q, p.j, d);
+#pragma unroll
+            for (int b = 0; b < 3; ++b) d[b] -= vi[q][b];
+            if constexpr (P::CELL) {
+                const double* T = o.shift(q, t >> 24);
+#pragma unroll
+                for (int b = 0; b < 3; ++b) d[b] += T[b];
+            }
+            acc[q] += P::Terms::dot(p, d);
+        }
+    };
+    emt_by_image<false>(a, i, &incomplete, visit);
+#pragma unroll
+    for (int q = 0; q < P::W; ++q) block_put<P::W>(part, q, acc[q]);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < P::W) o.c(t, i) = block_total<P::W>(part, t);
+}
+
+// (H v)_i = sum over the visits with j != i of  K d - u (F2_i c_i w'_ij + F2_j c_j w'_ji),  d = v_i - v_j (- T_q[s]):
+// g_i on atom i is -sum w'_ij u, g_j on atom i is -w'_ji u (atom i seen from j lies along -u).
+// CELL: nine more sums per vector, atom i's share of the cell rows: s_i[(k, b)] = sum over ALL visits of
+// n_k [F2_i c_i w'_ij u_b - 1/2 (K d)_b] (the 1/2 of the `B` formula; the first term is F2_i c_i gamma_i).
+// The NA = 3 or 12 sums of every vector are reduced behind one barrier; thread NA q + c then hands sum c of vector q to
+// store(q, c, sum).
+template <class P, class Store>
+__device__ __forceinline__ void emt_gather_body(const VB vb, const EmtArgs& a, const double* F2, const P& o, Store store) {
+    constexpr int NA = P::CELL ? 12 : 3;
+    __shared__ double part[4][NA * P::W];
+    __shared__ int incomplete;
+    const int i = vb.x;
+    const EmtAtom m = emt_atom(a, i);
+    const double f2i = F2[i];
+    double vi[P::W][3], fc[P::W], acc[P::W][NA];
+#pragma unroll
+    for (int q = 0; q < P::W; ++q) {
+        o.load(q, i, vi[q]);
+        fc[q] = f2i * o.c(q, i);
+#pragma unroll
+        for (int c = 0; c < NA; ++c) acc[q][c] = 0.0;
+    }
+    auto visit = [&](int t) {
+        EmtPair p;
+        if (!emt_pair<P::CELL>(a, m, t, p)) return;
+        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
+        const double f2j = F2[p.j];
+        double nv[3] = {0.0, 0.0, 0.0};
+        if constexpr (P::CELL) {
+            const double* ns = o.nimg + 3 * (t >> 24);
+            nv[0] = ns[0]; nv[1] = ns[1]; nv[2] = ns[2];
+        }
+#pragma unroll
+        for (int q = 0; q < P::W; ++q) {
+            double d[3];
+            o.load(q, p.j, d);
+#pragma unroll
+            for (int b = 0; b < 3; ++b) d[b] = vi[q][b] - d[b];
+            if constexpr (P::CELL) {
+                const double* T = o.shift(q, t >> 24);
+#pragma unroll
+                for (int b = 0; b < 3; ++b) d[b] -= T[b];
+            }
+            if (!P::CELL || p.j != i) P::Terms::row(p, c1, c2, d, fc[q], f2j * o.c(q, p.j), acc[q]);   // an own image moves no position block
+            if constexpr (P::CELL) {
+                const double u[3] = {p.ux, p.uy, p.uz};
+                const double along = c2 * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]), own = fc[q] * p.wp_ij;
+#pragma unroll
+                for (int b = 0; b < 3; ++b) {
+                    const double tb = own * u[b] - 0.5 * (c1 * d[b] + along * u[b]);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) acc[q][3 + 3 * k + b] += nv[k] * tb;
+                }
+            }
+        }
+    };
+    emt_by_image<false>(a, i, &incomplete, visit);
+#pragma unroll
+    for (int q = 0; q < P::W; ++q)
+#pragma unroll
+        for (int c = 0; c < NA; ++c) block_put<NA * P::W>(part, NA * q + c, acc[q][c]);
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < NA * P::W) store(t / NA, t % NA, block_total<NA * P::W>(part, t));
+}
+
+// Vectors q0 .. q0 + KQ - 1 of the rows of a host product: every array holds round_up(k, KQ) rows, those of V (and T)
+// beyond k zero; the dots vector-major
+template <int KQ, bool CELL_>
+struct EmtRows {
+    using Terms = EmtTerms;
+    static constexpr int W = KQ;
+    static constexpr bool CELL = CELL_;
+    const double* V; size_t ld;             // (k, ld), atom j of a row at 3 j
+    double* cdot; int n;                    // (k, n)
+    int q0;
+    const double* nimg; const double* T; int nshift;          // CELL: n_s (nshift x 3) and T_q[s] = n_s W_q (k, nshift, 3)
+    __device__ __forceinline__ void load(int q, int j, double x[3]) const {
+        const double* v = V + (size_t)(q0 + q) * ld + 3 * j;
+        x[0] = v[0]; x[1] = v[1]; x[2] = v[2];
+    }
+    __device__ __forceinline__ double& c(int q, int j) const { return cdot[(size_t)(q0 + q) * n + j]; }
+    __device__ __forceinline__ const double* shift(int q, int s) const { return T + ((size_t)(q0 + q) * nshift + s) * 3; }
+};
+
+struct EmtHvp {                             // k vectors
     const double* F2;
     const double* V;                        // (k, 3n)
     double* cdot;                           // (k, n): c_i = g_i . v
     double* HV;                             // (k, 3n)
 };
-
-// c_i[q] = g_i . v_q = sum over the pairs of w' u . (v_j - v_i), vectors KQ vb.y .. of the product
 template <int KQ>
-__device__ __forceinline__ void emt_hvp_dots_body(const VB vb, const EmtArgs& a, const EmtHvp& o) {
-    __shared__ double red[4];
-    __shared__ int incomplete;
-    const int i = vb.x, q0 = vb.y * KQ;
-    const size_t n3 = (size_t)3 * a.n;
-    const EmtAtom m = emt_atom(a, i);
-    double vi[KQ][3], acc[KQ];
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * i;
-        vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
-        acc[q] = 0.0;
-    }
-    auto visit = [&](int t) {
-        EmtPair p;
-        if (!emt_pair(a, m, t, p)) return;
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) {
-            const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * p.j;
-            acc[q] += p.wp_ij * (p.ux * (v[0] - vi[q][0]) + p.uy * (v[1] - vi[q][1]) + p.uz * (v[2] - vi[q][2]));
-        }
-    };
-    emt_by_image<false>(a, i, &incomplete, visit);
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        const double s = block_sum(acc[q], red);
-        if (threadIdx.x == 0) o.cdot[(size_t)(q0 + q) * a.n + i] = s;
-    }
+__device__ __forceinline__ EmtRows<KQ, false> emt_rows(const VB vb, const EmtArgs& a, const EmtHvp& o) {
+    return {o.V, (size_t)3 * a.n, o.cdot, a.n, (int)vb.y * KQ, nullptr, nullptr, 0};
 }
-__device__ __forceinline__ void emt_hvp_dots_vb(const VB vb, EmtArgs a, EmtHvp o) { emt_hvp_dots_body<HVP_KQ>(vb, a, o); }
+
+__device__ __forceinline__ void emt_hvp_dots_vb(const VB vb, EmtArgs a, EmtHvp o) { emt_dots_body(vb, a, emt_rows<HVP_KQ>(vb, a, o)); }
 __global__ __launch_bounds__(256) void emt_hvp_dots_kernel(EmtArgs a, EmtHvp o) { emt_hvp_dots_vb(vb_hw(), a, o); }
-__device__ __forceinline__ void emt_hvp1_dots_vb(const VB vb, EmtArgs a, EmtHvp o) { emt_hvp_dots_body<1>(vb, a, o); }
+__device__ __forceinline__ void emt_hvp1_dots_vb(const VB vb, EmtArgs a, EmtHvp o) { emt_dots_body(vb, a, emt_rows<1>(vb, a, o)); }
 __global__ __launch_bounds__(256) void emt_hvp1_dots_kernel(EmtArgs a, EmtHvp o) { emt_hvp1_dots_vb(vb_hw(), a, o); }
 
-// (H v)_i = sum over the pairs of  -u (F2_i c_i w'_ij + F2_j c_j w'_ji)  +  K (v_i - v_j):
-// g_i on atom i is -sum w'_ij u, g_j on atom i is -w'_ji u (atom i seen from j lies along -u)
-// store(q, sx, sy, sz), on thread 0: where the three components of vector q0 + q go
-template <int KQ, class Store>
-__device__ __forceinline__ void emt_hvp_gather_body(const VB vb, const EmtArgs& a, const EmtHvp& o, Store store) {
-    __shared__ double red[4];
-    __shared__ int incomplete;
-    const int i = vb.x, q0 = vb.y * KQ;
-    const size_t n3 = (size_t)3 * a.n;
-    const EmtAtom m = emt_atom(a, i);
-    const double f2i = o.F2[i];
-    double vi[KQ][3], fc[KQ], acc[KQ][3];
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * i;
-        vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
-        fc[q] = f2i * o.cdot[(size_t)(q0 + q) * a.n + i];
-        acc[q][0] = acc[q][1] = acc[q][2] = 0.0;
-    }
-    auto visit = [&](int t) {
-        EmtPair p;
-        if (!emt_pair(a, m, t, p)) return;
-        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;
-        const double f2j = o.F2[p.j];
-#pragma unroll
-        for (int q = 0; q < KQ; ++q) {
-            const double* v = o.V + (size_t)(q0 + q) * n3 + 3 * p.j;
-            const double dx = vi[q][0] - v[0], dy = vi[q][1] - v[1], dz = vi[q][2] - v[2];
-            const double along = c2 * (p.ux * dx + p.uy * dy + p.uz * dz)
-                                 - (fc[q] * p.wp_ij + f2j * o.cdot[(size_t)(q0 + q) * a.n + p.j] * p.wp_ji);
-            acc[q][0] += c1 * dx + along * p.ux;
-            acc[q][1] += c1 * dy + along * p.uy;
-            acc[q][2] += c1 * dz + along * p.uz;
-        }
-    };
-    emt_by_image<false>(a, i, &incomplete, visit);
-#pragma unroll
-    for (int q = 0; q < KQ; ++q) {
-        const double sx = block_sum(acc[q][0], red), sy = block_sum(acc[q][1], red), sz = block_sum(acc[q][2], red);
-        if (threadIdx.x == 0) store(q, sx, sy, sz);
-    }
-}
 __device__ __forceinline__ void emt_hvp_gather_vb(const VB vb, EmtArgs a, EmtHvp o) {
-    const size_t n3 = (size_t)3 * a.n;
-    emt_hvp_gather_body<HVP_KQ>(vb, a, o, [&](int q, double sx, double sy, double sz) {
-        double* out = o.HV + (size_t)(vb.y * HVP_KQ + q) * n3 + 3 * vb.x;
-        out[0] = sx; out[1] = sy; out[2] = sz;
-    });
+    const auto rows = emt_rows<HVP_KQ>(vb, a, o);
+    emt_gather_body(vb, a, o.F2, rows, [&](int q, int c, double v) { o.HV[(rows.q0 + q) * rows.ld + 3 * vb.x + c] = v; });
 }
 __global__ __launch_bounds__(256) void emt_hvp_gather_kernel(EmtArgs a, EmtHvp o) { emt_hvp_gather_vb(vb_hw(), a, o); }
 
@@ -323,15 +437,11 @@ __device__ __forceinline__ void emt_hvp1_gather_vb(const VB vb, EmtArgs a, EmtHv
     s = block_sum(s, red1);
     const bool live = !(sqrt(s) < 1e-12);
     if (vb.x == 0 && threadIdx.x == 0) *w.flag = live ? 1 : 0;
-    emt_hvp_gather_body<1>(vb, a, o, [&](int, double sx, double sy, double sz) {
-        const int p = 3 * vb.x;
-        const double h[3] = {live ? sx : 0.0, live ? sy : 0.0, live ? sz : 0.0};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            o.HV[p + k] = h[k];
-            const int q = w.inv ? w.inv[p + k] : p + k;
-            if (q >= 0) w.y[q] = h[k];
-        }
+    emt_gather_body(vb, a, o.F2, emt_rows<1>(vb, a, o), [&](int, int c, double v) {
+        const int p = 3 * vb.x + c, q = w.inv ? w.inv[p] : p;
+        const double h = live ? v : 0.0;
+        o.HV[p] = h;
+        if (q >= 0) w.y[q] = h;
     });
 }
 __global__ __launch_bounds__(256) void emt_hvp1_gather_kernel(EmtArgs a, EmtHvp o, EmtHvpOut1 w) { emt_hvp1_gather_vb(vb_hw(), a, o, w); }
@@ -339,127 +449,39 @@ __global__ __launch_bounds__(256) void emt_hvp1_gather_kernel(EmtArgs a, EmtHvp 
 // ---- the block product of the operator (calc.hip, hvp_device_apply_block) -------------------------------------------------
 // Up to HVB_W vectors, the rows of a device panel (row h at V + h ldv: the eigensolver's own panel when all 3n coordinates
 // are free, else the full-length rows a scatter filled), on the operator's resident state.  One workgroup per atom carries
-// all HVB_W vectors: the pair quantities of a visit are evaluated once for all of them (48 accumulators per thread in the
-// gather pass; 8 per workgroup, and a panel staged atom-major, were measured and lost: profiles/block_hvp.md).  The dots
-// c_j are kept atom-major.  Rows beyond nh are never read (the row index is clamped: their slots repeat row nh - 1 and are
-// not stored).  Every vector's sums are taken in the order of the single-vector kernels and every product is rounded on its
-// own (no contraction into fused multiply-adds, which the compiler chooses slot by slot in the unrolled loops: measured, the
-// same vector in slot 0 and in slot 11 differed in the last bit), so a row's result does not depend on which row it is, on
-// what stands in the other rows, or on nh.
+// all HVB_W vectors (48 accumulators per thread in the gather pass; 8 per workgroup, and a panel staged atom-major, were
+// measured and lost: profiles/block_hvp.md).  The dots c_j are kept atom-major.  Rows beyond nh are never read (the row
+// index is clamped: their slots repeat row nh - 1 and are not stored).  Every vector's sums are taken in the order of the
+// single-vector kernels and every product is rounded on its own (no contraction into fused multiply-adds, which the
+// compiler chooses slot by slot in the unrolled loops: measured, the same vector in slot 0 and in slot 11 differed in the
+// last bit), so a row's result does not depend on which row it is, on what stands in the other rows, or on nh.
 constexpr int HVB_W = 16;
 
 struct EmtHvpB {
+    using Terms = EmtTermsExact;
+    static constexpr int W = HVB_W;
+    static constexpr bool CELL = false;
     const double* F2;
     const double* V; int ldv;               // the panel
     int nh;
     double* cdot;                           // n x HVB_W: c_j of vector q at [HVB_W j + q]
     const int* inv;                         // full coordinate -> column of Y, -1 if pinned; null: all free
     double* Y; int ldy;                     // (nh, m): the free rows of the products
+    __device__ __forceinline__ void load(int q, int j, double x[3]) const {
+        const double* v = V + (size_t)(q < nh ? q : nh - 1) * ldv + 3 * j;
+        x[0] = v[0]; x[1] = v[1]; x[2] = v[2];
+    }
+    __device__ __forceinline__ double& c(int q, int j) const { return cdot[(size_t)j * HVB_W + q]; }
 };
 
-__device__ __forceinline__ void hvb_load(const EmtHvpB& o, int q, int j, double& x, double& y, double& z) {
-    const double* v = o.V + (size_t)(q < o.nh ? q : o.nh - 1) * o.ldv + 3 * j;
-    x = v[0]; y = v[1]; z = v[2];
-}
-
-// block_sum's arithmetic for NS sums behind ONE barrier (as emt_cell_pair): the wavefronts' sums side by side in LDS; after
-// the barrier thread t < NS reads sum t with hvb_total
-template <int NS>
-__device__ __forceinline__ void hvb_put(double (*part)[NS], int slot, double v) {
-    v = wave_sum64(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][slot] = v;
-}
-template <int NS>
-__device__ __forceinline__ double hvb_total(const double (*part)[NS], int slot) {
-    return (part[0][slot] + part[1][slot]) + (part[2][slot] + part[3][slot]);
-}
-
-__device__ __forceinline__ void emt_hvpb_dots_vb(const VB vb, EmtArgs a, EmtHvpB o) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-    __shared__ double part[4][HVB_W];
-    __shared__ int incomplete;
-    const int i = vb.x;
-    const EmtAtom m = emt_atom(a, i);
-    double vi[HVB_W][3], acc[HVB_W];
-#pragma unroll
-    for (int q = 0; q < HVB_W; ++q) {
-        hvb_load(o, q, i, vi[q][0], vi[q][1], vi[q][2]);
-        acc[q] = 0.0;
-    }
-    auto visit = [&](int t) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-        EmtPair p;
-        if (!emt_pair(a, m, t, p)) return;
-#pragma unroll
-        for (int q = 0; q < HVB_W; ++q) {
-            double v0, v1, v2;
-            hvb_load(o, q, p.j, v0, v1, v2);
-            acc[q] += p.wp_ij * (p.ux * (v0 - vi[q][0]) + p.uy * (v1 - vi[q][1]) + p.uz * (v2 - vi[q][2]));
-        }
-    };
-    emt_by_image<false>(a, i, &incomplete, visit);
-#pragma unroll
-    for (int q = 0; q < HVB_W; ++q) hvb_put<HVB_W>(part, q, acc[q]);
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < HVB_W) o.cdot[(size_t)i * HVB_W + t] = hvb_total<HVB_W>(part, t);
-}
+__device__ __forceinline__ void emt_hvpb_dots_vb(const VB vb, EmtArgs a, EmtHvpB o) { emt_dots_body(vb, a, o); }
 __global__ __launch_bounds__(256) void emt_hvpb_dots_kernel(EmtArgs a, EmtHvpB o) { emt_hvpb_dots_vb(vb_hw(), a, o); }
 
 __device__ __forceinline__ void emt_hvpb_gather_vb(const VB vb, EmtArgs a, EmtHvpB o) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-    __shared__ double part[4][3 * HVB_W];
-    __shared__ int incomplete;
-    const int i = vb.x;
-    const EmtAtom m = emt_atom(a, i);
-    const double f2i = o.F2[i];
-    double vi[HVB_W][3], fc[HVB_W], acc[HVB_W][3];
-#pragma unroll
-    for (int q = 0; q < HVB_W; ++q) {
-        hvb_load(o, q, i, vi[q][0], vi[q][1], vi[q][2]);
-        fc[q] = f2i * o.cdot[(size_t)i * HVB_W + q];
-        acc[q][0] = acc[q][1] = acc[q][2] = 0.0;
-    }
-    auto visit = [&](int t) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-        EmtPair p;
-        if (!emt_pair(a, m, t, p)) return;
-        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;
-        const double f2j = o.F2[p.j];
-        const double* cj = o.cdot + (size_t)p.j * HVB_W;
-#pragma unroll
-        for (int q = 0; q < HVB_W; ++q) {
-            double v0, v1, v2;
-            hvb_load(o, q, p.j, v0, v1, v2);
-            const double dx = vi[q][0] - v0, dy = vi[q][1] - v1, dz = vi[q][2] - v2;
-            const double along = c2 * (p.ux * dx + p.uy * dy + p.uz * dz) - (fc[q] * p.wp_ij + f2j * cj[q] * p.wp_ji);
-            acc[q][0] += c1 * dx + along * p.ux;
-            acc[q][1] += c1 * dy + along * p.uy;
-            acc[q][2] += c1 * dz + along * p.uz;
-        }
-    };
-    emt_by_image<false>(a, i, &incomplete, visit);
-#pragma unroll
-    for (int q = 0; q < HVB_W; ++q) {
-        hvb_put<3 * HVB_W>(part, 3 * q, acc[q][0]);
-        hvb_put<3 * HVB_W>(part, 3 * q + 1, acc[q][1]);
-        hvb_put<3 * HVB_W>(part, 3 * q + 2, acc[q][2]);
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t >= 3 * HVB_W) return;
-    const int q = t / 3, p = 3 * i + t % 3;
-    if (q >= o.nh) return;
-    const int r = o.inv ? o.inv[p] : p;
-    if (r >= 0) o.Y[(size_t)q * o.ldy + r] = hvb_total<3 * HVB_W>(part, t);
+    emt_gather_body(vb, a, o.F2, o, [&](int q, int c, double v) {
+        const int p = 3 * vb.x + c, r = o.inv ? o.inv[p] : p;
+        if (q < o.nh && r >= 0) o.Y[(size_t)q * o.ldy + r] = v;
+    });
 }
 __global__ __launch_bounds__(256) void emt_hvpb_gather_kernel(EmtArgs a, EmtHvpB o) { emt_hvpb_gather_vb(vb_hw(), a, o); }
 
@@ -480,11 +502,12 @@ __device__ __forceinline__ void emt_hdiag_vb(const VB vb, EmtArgs a, const doubl
         for (int s = 0; s < a.nshift; ++s) {
             EmtPair p;
             if (!emt_pair(a, m, emt_pack(j, s), p)) continue;
-            const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
+            double K[6];
+            emt_pair_K(p, K);
             const double u[3] = {p.ux, p.uy, p.uz};
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                k[c] += c1 + c2 * (u[c] * u[c]);
+                k[c] += K[c];
                 g[c] -= p.wp_ij * u[c];
                 h[c] -= p.wp_ji * u[c];
             }
@@ -495,24 +518,21 @@ __device__ __forceinline__ void emt_hdiag_vb(const VB vb, EmtArgs a, const doubl
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        hvb_put<9>(part, c, k[c]);
-        hvb_put<9>(part, 3 + c, g[c]);
-        hvb_put<9>(part, 6 + c, e[c]);
+        block_put<9>(part, c, k[c]);
+        block_put<9>(part, 3 + c, g[c]);
+        block_put<9>(part, 6 + c, e[c]);
     }
     __syncthreads();
     const int t = threadIdx.x;
     if (t >= 3) return;
-    const double gi = hvb_total<9>(part, 3 + t);
+    const double gi = block_total<9>(part, 3 + t);
     const int p = 3 * i + t, r = inv ? inv[p] : p;
-    if (r >= 0) y[r] = hvb_total<9>(part, t) + F2[i] * (gi * gi) + hvb_total<9>(part, 6 + t);
+    if (r >= 0) y[r] = block_total<9>(part, t) + F2[i] * (gi * gi) + block_total<9>(part, 6 + t);
 }
 __global__ __launch_bounds__(256) void emt_hdiag_kernel(EmtArgs a, const double* __restrict__ F2, const int* __restrict__ inv,
                                                         double* __restrict__ y) { emt_hdiag_vb(vb_hw(), a, F2, inv, y); }
 
 // ---- the cell columns ---------------------------------------------------------------------------------------------------
-// symmetric index of (a, b), a, b in 0..2, in the order xx, yy, zz, yz, xz, xy
-__host__ __device__ __forceinline__ int sym6(int a, int b) { return a == b ? a : 6 - a - b; }
-
 struct EmtCell {
     const double* F2;
     const double* nimg;                     // nshift x 3: n_s = S_s C^-1, whole numbers
@@ -545,9 +565,8 @@ __device__ __forceinline__ void emt_cell_pair_vb(const VB vb, EmtArgs a, EmtCell
         if (nv[0] == 0.0 && nv[1] == 0.0 && nv[2] == 0.0) return;                 // the home image: no cell in d
         EmtPair p;
         if (!emt_pair<true>(a, m, t, p)) return;
-        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
-        const double K[6] = {c1 + c2 * (p.ux * p.ux), c1 + c2 * (p.uy * p.uy), c1 + c2 * (p.uz * p.uz),
-                             c2 * (p.uy * p.uz), c2 * (p.ux * p.uz), c2 * (p.ux * p.uy)};
+        double K[6];
+        emt_pair_K(p, K);
         const double wu[3] = {p.wp_ij * p.ux, p.wp_ij * p.uy, p.wp_ij * p.uz};
         const double nn[6] = {nv[0] * nv[0], nv[1] * nv[1], nv[2] * nv[2], nv[1] * nv[2], nv[0] * nv[2], nv[0] * nv[1]};
         const double other = p.j != i ? 1.0 : 0.0;                                // an own image moves no position block
@@ -565,28 +584,21 @@ __device__ __forceinline__ void emt_cell_pair_vb(const VB vb, EmtArgs a, EmtCell
             for (int q = 0; q < 6; ++q) kk[pq][q] += K[q] * nn[pq];
     };
     emt_by_image<false>(a, i, &incomplete, visit);
-    // block_sum's arithmetic for all 63 sums behind one barrier: the wavefronts' sums side by side in LDS, then thread
-    // t adds those of sum t and stores it
-    const int wave = threadIdx.x >> 6;
-    auto put = [&](int slot, double v) {
-        v = wave_sum64(v);
-        if ((threadIdx.x & 63) == 0) part[wave][slot] = v;
-    };
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
 #pragma unroll
-        for (int q = 0; q < 6; ++q) put(6 * k + q, kn[k][q]);
+        for (int q = 0; q < 6; ++q) block_put<63>(part, 6 * k + q, kn[k][q]);
 #pragma unroll
-        for (int b = 0; b < 3; ++b) put(18 + 3 * k + b, gk[k][b]);
+        for (int b = 0; b < 3; ++b) block_put<63>(part, 18 + 3 * k + b, gk[k][b]);
     }
 #pragma unroll
     for (int p = 0; p < 6; ++p)
 #pragma unroll
-        for (int q = 0; q < 6; ++q) put(27 + 6 * p + q, kk[p][q]);
+        for (int q = 0; q < 6; ++q) block_put<63>(part, 27 + 6 * p + q, kk[p][q]);
     __syncthreads();
     const int t = threadIdx.x;
     if (t >= 63) return;
-    const double v = (part[0][t] + part[1][t]) + (part[2][t] + part[3][t]);
+    const double v = block_total<63>(part, t);
     if (t < 18) {                           // - sum K_rb n_k into A[(i, r), (k, b)], both (r, b) of an off-diagonal component
         const int k = t / 6, q = t % 6, n3 = 3 * a.n;
         for (int r = 0; r < 3; ++r)
@@ -679,104 +691,20 @@ struct EmtCellHvp {                         // k vectors: every array holds roun
     double* cdot;                           // (k, n): c_i = sum_visits w'_ij u . dd
     double* share;                          // (k, n, 9): atom i's share of the cell rows, column 3 k + b
 };
-
-// c_i[q] = g_i . v_q + gamma_i . W_q = sum over ALL visits of atom i (its own images too: dd = T_q[s] there) of w' u . dd
-__device__ __forceinline__ void emt_chvp_dots_vb(const VB vb, EmtArgs a, EmtCellHvp o) {
-    __shared__ double part[4][CHVP_KQ];
-    __shared__ int incomplete;
-    const int i = vb.x, q0 = vb.y * CHVP_KQ;
-    const EmtAtom m = emt_atom(a, i);
-    double vi[CHVP_KQ][3], acc[CHVP_KQ];
-#pragma unroll
-    for (int q = 0; q < CHVP_KQ; ++q) {
-        const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * i;
-        vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
-        acc[q] = 0.0;
-    }
-    auto visit = [&](int t) {
-        EmtPair p;
-        if (!emt_pair<true>(a, m, t, p)) return;
-        const int s = t >> 24;
-#pragma unroll
-        for (int q = 0; q < CHVP_KQ; ++q) {
-            const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * p.j;
-            const double* T = o.T + ((size_t)(q0 + q) * a.nshift + s) * 3;
-            const double dx = v[0] - vi[q][0] + T[0], dy = v[1] - vi[q][1] + T[1], dz = v[2] - vi[q][2] + T[2];
-            acc[q] += p.wp_ij * (p.ux * dx + p.uy * dy + p.uz * dz);
-        }
-    };
-    emt_by_image<false>(a, i, &incomplete, visit);
-#pragma unroll
-    for (int q = 0; q < CHVP_KQ; ++q) hvb_put<CHVP_KQ>(part, q, acc[q]);
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t < CHVP_KQ) o.cdot[(size_t)(q0 + t) * a.n + i] = hvb_total<CHVP_KQ>(part, t);
+__device__ __forceinline__ EmtRows<CHVP_KQ, true> emt_rows(const VB vb, const EmtArgs& a, const EmtCellHvp& o) {
+    return {o.V, (size_t)o.ld, o.cdot, a.n, (int)vb.y * CHVP_KQ, o.nimg, o.T, a.nshift};
 }
+
+__device__ __forceinline__ void emt_chvp_dots_vb(const VB vb, EmtArgs a, EmtCellHvp o) { emt_dots_body(vb, a, emt_rows(vb, a, o)); }
 __global__ __launch_bounds__(256) void emt_chvp_dots_kernel(EmtArgs a, EmtCellHvp o) { emt_chvp_dots_vb(vb_hw(), a, o); }
 
-// position rows: (y_x)_i = - sum over the visits with j != i of [K dd + u (F2_i c_i w'_ij + F2_j c_j w'_ji)]
-// cell rows, atom i's share: s_i[(k, b)] = sum over ALL visits of n_k [1/2 (K dd)_b + F2_i c_i w'_ij u_b] (the 1/2 of the
-// `B` formula; the second term is F2_i c_i gamma_i).  The twelve sums of a vector are reduced behind one barrier.
+// sums 0 .. 2 of a vector: its position rows of atom i; 3 .. 11: the atom's share of its cell rows
 __device__ __forceinline__ void emt_chvp_gather_vb(const VB vb, EmtArgs a, EmtCellHvp o) {
-    constexpr int NS = 12 * CHVP_KQ;
-    __shared__ double part[4][NS];
-    __shared__ int incomplete;
-    const int i = vb.x, q0 = vb.y * CHVP_KQ;
-    const EmtAtom m = emt_atom(a, i);
-    const double f2i = o.F2[i];
-    double vi[CHVP_KQ][3], fc[CHVP_KQ], ax[CHVP_KQ][3], ac[CHVP_KQ][9];
-#pragma unroll
-    for (int q = 0; q < CHVP_KQ; ++q) {
-        const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * i;
-        vi[q][0] = v[0]; vi[q][1] = v[1]; vi[q][2] = v[2];
-        fc[q] = f2i * o.cdot[(size_t)(q0 + q) * a.n + i];
-        ax[q][0] = ax[q][1] = ax[q][2] = 0.0;
-#pragma unroll
-        for (int c = 0; c < 9; ++c) ac[q][c] = 0.0;
-    }
-    auto visit = [&](int t) {
-        EmtPair p;
-        if (!emt_pair<true>(a, m, t, p)) return;
-        const int s = t >> 24;
-        const double* ns = o.nimg + 3 * s;
-        const double nv[3] = {ns[0], ns[1], ns[2]};
-        const double c1 = p.e1 / p.r, c2 = p.e2 - c1;                             // K = c1 I + c2 u u^T
-        const double f2j = o.F2[p.j];
-        const double other = p.j != i ? 1.0 : 0.0;                                // an own image moves no position block
-#pragma unroll
-        for (int q = 0; q < CHVP_KQ; ++q) {
-            const double* v = o.V + (size_t)(q0 + q) * o.ld + 3 * p.j;
-            const double* T = o.T + ((size_t)(q0 + q) * a.nshift + s) * 3;
-            const double dx = v[0] - vi[q][0] + T[0], dy = v[1] - vi[q][1] + T[1], dz = v[2] - vi[q][2] + T[2];
-            const double along = c2 * (p.ux * dx + p.uy * dy + p.uz * dz);
-            const double kd[3] = {c1 * dx + along * p.ux, c1 * dy + along * p.uy, c1 * dz + along * p.uz};   // K dd
-            const double own = fc[q] * p.wp_ij;
-            const double emb = other * (own + f2j * o.cdot[(size_t)(q0 + q) * a.n + p.j] * p.wp_ji);
-            const double u[3] = {p.ux, p.uy, p.uz};
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                ax[q][b] -= other * kd[b] + emb * u[b];
-                const double tb = 0.5 * kd[b] + own * u[b];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) ac[q][3 * k + b] += nv[k] * tb;
-            }
-        }
-    };
-    emt_by_image<false>(a, i, &incomplete, visit);
-#pragma unroll
-    for (int q = 0; q < CHVP_KQ; ++q) {
-#pragma unroll
-        for (int b = 0; b < 3; ++b) hvb_put<NS>(part, 12 * q + b, ax[q][b]);
-#pragma unroll
-        for (int c = 0; c < 9; ++c) hvb_put<NS>(part, 12 * q + 3 + c, ac[q][c]);
-    }
-    __syncthreads();
-    const int t = threadIdx.x;
-    if (t >= NS) return;
-    const int q = q0 + t / 12, c = t % 12;
-    const double v = hvb_total<NS>(part, t);
-    if (c < 3) o.HV[(size_t)q * o.ld + 3 * i + c] = v;
-    else o.share[((size_t)q * a.n + i) * 9 + (c - 3)] = v;
+    const auto rows = emt_rows(vb, a, o);
+    emt_gather_body(vb, a, o.F2, rows, [&](int q, int c, double v) {
+        if (c < 3) o.HV[(rows.q0 + q) * rows.ld + 3 * vb.x + c] = v;
+        else o.share[((size_t)(rows.q0 + q) * a.n + vb.x) * 9 + (c - 3)] = v;
+    });
 }
 __global__ __launch_bounds__(256) void emt_chvp_gather_kernel(EmtArgs a, EmtCellHvp o) { emt_chvp_gather_vb(vb_hw(), a, o); }
 
@@ -794,10 +722,10 @@ __device__ __forceinline__ void emt_chvp_finish_vb(const VB vb, int n, EmtCellHv
         for (int c = 0; c < 9; ++c) acc[c] += s[c];
     }
 #pragma unroll
-    for (int c = 0; c < 9; ++c) hvb_put<9>(part, c, acc[c]);
+    for (int c = 0; c < 9; ++c) block_put<9>(part, c, acc[c]);
     __syncthreads();
     const int t = threadIdx.x;
-    if (t < 9) o.HV[(size_t)q * o.ld + 3 * n + t] = hvb_total<9>(part, t);
+    if (t < 9) o.HV[(size_t)q * o.ld + 3 * n + t] = block_total<9>(part, t);
 }
 __global__ __launch_bounds__(256) void emt_chvp_finish_kernel(int n, EmtCellHvp o) { emt_chvp_finish_vb(vb_hw(), n, o); }
 
@@ -816,13 +744,31 @@ struct TempMats {                           // device matrices of one call, back
 
 using namespace sella;
 
+// What every entry does first: the density pass queued (emt_density_queue: dconst and the scratch slot as there) and F2
+// behind it.  *F2 holds n numbers; the caller's `extra_words` doubles follow it.
+static int emt_f2_queue(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                        const double* dconst, double rc, double acut, double cutoff, double beta, size_t extra_words, EmtArgs* a,
+                        double** F2) {
+    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, (size_t)n + extra_words, a, F2));
+    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, *a, *F2);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
+// The k rows of `len` numbers of a host array to the device, the rows up to kp (k rounded up to the vectors of a
+// workgroup) zero
+static int emt_upload_rows(sella_ctx* c, double* dst, const double* src, int k, size_t kp, size_t len) {
+    SCHK(h2d_async(c, dst, src, (size_t)k * len * sizeof(double)));
+    if (kp > (size_t)k) HIPCHK(s_memset0(c, dst + (size_t)k * len, (kp - k) * len * sizeof(double)));
+    return SELLA_OK;
+}
+
 // The passes of the dense Hessian into the leading 3n x 3n block of H (rows ldh apart, zero on entry), symmetrised.
 // G^T and diag(F2) G^T (n x 3n) stay behind in t.h[0], t.h[1].
 static int emt_hessian_block(sella_ctx* c, int n, const EmtArgs& a, double* F2, double* H, int ldh, TempMats& t) {
     SCHK(mat_new(c, n, 3 * n, &t.h[0]));                              // zeroed: the visits add into the rows
     SCHK(mat_new(c, n, 3 * n, &t.h[1]));
     Mat *Gt = mat_get(c, t.h[0]), *Gs = mat_get(c, t.h[1]);
-    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, F2);
     EmtHessOut o;
     o.F2 = F2; o.H = H; o.ldh = ldh; o.Gt = Gt->d; o.Gs = Gs->d; o.ldg = Gt->ld;
     SELLA_LAUNCHB(c, emt_hess_pair_kernel, emt_hess_pair_vb, 256, dim3(n), dim3(256), 0, a, o);
@@ -843,7 +789,7 @@ int sella::emt_hessian_resident(sella_ctx* c, int n, const double* pos, const do
     }
     EmtArgs a;
     double* F2;
-    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, (size_t)n, &a, &F2));
+    SCHK(emt_f2_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, 0, &a, &F2));
     TempMats t(c);
     HIPCHK(s_memset0(c, H->d, (size_t)H->rows * H->ld * sizeof(double)));
     SCHK(emt_hessian_block(c, n, a, F2, H->d, H->ld, t));
@@ -853,6 +799,8 @@ int sella::emt_hessian_resident(sella_ctx* c, int n, const double* pos, const do
 // Image indices n_s = S_s C^-1 of the shifts in the cell (lattice vectors in the rows of C): whole numbers, or the
 // shifts are no lattice translations of this cell.
 static int emt_image_indices(const double* cell, int nshift, const double* shifts, std::vector<double>& nimg) {
+    // (emt_density_queue's limit, here before `shifts` is read)
+    if (nshift > 127) { set_error("emt: at most 2^24 atoms and 127 periodic images"); return SELLA_E_INVALID; }
     const double* C = cell;
     const double cof[9] = {C[4] * C[8] - C[5] * C[7], C[2] * C[7] - C[1] * C[8], C[1] * C[5] - C[2] * C[4],
                            C[5] * C[6] - C[3] * C[8], C[0] * C[8] - C[2] * C[6], C[2] * C[3] - C[0] * C[5],
@@ -892,13 +840,12 @@ extern "C" int sella_emt_cell_hessian(sella_ctx* c, int n, const double* pos, co
         set_error("emt_cell_hessian: out must be the %d x %d matrix of %d atoms and the cell", dim, dim, n);
         return SELLA_E_INVALID;
     }
-    if (nshift > 127) { set_error("emt: at most 2^24 atoms and 127 periodic images"); return SELLA_E_INVALID; }
     std::vector<double> nimg;
     SCHK(emt_image_indices(cell, nshift, shifts, nimg));
     EmtArgs a;
     double* ex;                                                       // F2 (n), image indices (3 nshift), shares of B (36 n)
-    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta,
-                           (size_t)n + (size_t)3 * nshift + (size_t)36 * n, &a, &ex));
+    SCHK(emt_f2_queue(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta, (size_t)3 * nshift + (size_t)36 * n, &a,
+                      &ex));
     double* dn = ex + n;
     SCHK(h2d_async(c, dn, nimg.data(), nimg.size() * sizeof(double)));
     TempMats t(c);
@@ -929,7 +876,6 @@ extern "C" int sella_emt_cell_hvp(sella_ctx* c, int n, const double* pos, const 
         set_error("emt_cell_hvp: invalid arguments");
         return SELLA_E_INVALID;
     }
-    if (nshift > 127) { set_error("emt: at most 2^24 atoms and 127 periodic images"); return SELLA_E_INVALID; }
     std::vector<double> nimg;
     SCHK(emt_image_indices(cell, nshift, shifts, nimg));
     const size_t dim = (size_t)3 * n + 9, kp = (size_t)round_up(k, CHVP_KQ), nT = (size_t)3 * nshift;
@@ -942,8 +888,8 @@ extern "C" int sella_emt_cell_hvp(sella_ctx* c, int n, const double* pos, const 
     }
     EmtArgs a;
     double* ex;                     // F2 (n), image indices (3 nshift), T (kp 3 nshift), V and HV (kp dim each), dots (kp n), shares (kp 9 n)
-    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta,
-                           (size_t)n + nT + kp * (nT + 2 * dim + (size_t)10 * n), &a, &ex));
+    SCHK(emt_f2_queue(c, n, pos, par, nshift, shifts, nullptr, rc, acut, cutoff, beta, nT + kp * (nT + 2 * dim + (size_t)10 * n),
+                      &a, &ex));
     double* dn = ex + n;
     double* dT = dn + nT;
     double* dV = dT + kp * nT;
@@ -952,9 +898,7 @@ extern "C" int sella_emt_cell_hvp(sella_ctx* c, int n, const double* pos, const 
     o.cdot = o.HV + kp * dim; o.share = o.cdot + kp * n;
     SCHK(h2d_async(c, dn, nimg.data(), nT * sizeof(double)));
     SCHK(h2d_async(c, dT, T.data(), kp * nT * sizeof(double)));
-    SCHK(h2d_async(c, dV, V, (size_t)k * dim * sizeof(double)));
-    if (kp > (size_t)k) HIPCHK(s_memset0(c, dV + (size_t)k * dim, (kp - k) * dim * sizeof(double)));
-    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, ex);
+    SCHK(emt_upload_rows(c, dV, V, k, kp, dim));
     const dim3 grid(n, (unsigned)(kp / CHVP_KQ));
     SELLA_LAUNCHB(c, emt_chvp_dots_kernel, emt_chvp_dots_vb, 256, grid, dim3(256), 0, a, o);
     SELLA_LAUNCHB(c, emt_chvp_gather_kernel, emt_chvp_gather_vb, 256, grid, dim3(256), 0, a, o);
@@ -971,14 +915,11 @@ int sella::emt_hvp_resident(sella_ctx* c, int n, const double* pos, const double
     const size_t n3 = (size_t)3 * n, kp = (size_t)round_up(k, HVP_KQ);
     EmtArgs a;
     double* ex;
-    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, (size_t)n + kp * (2 * n3 + n), &a,
-                           &ex));
+    SCHK(emt_f2_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, kp * (2 * n3 + n), &a, &ex));
     EmtHvp o;
     double* dV = ex + n;
     o.F2 = ex; o.V = dV; o.cdot = dV + kp * n3; o.HV = o.cdot + kp * n;
-    SCHK(h2d_async(c, dV, V, (size_t)k * n3 * sizeof(double)));
-    if (kp > (size_t)k) HIPCHK(s_memset0(c, dV + (size_t)k * n3, (kp - k) * n3 * sizeof(double)));
-    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, ex);
+    SCHK(emt_upload_rows(c, dV, V, k, kp, n3));
     const dim3 grid(n, (unsigned)(kp / HVP_KQ));
     SELLA_LAUNCHB(c, emt_hvp_dots_kernel, emt_hvp_dots_vb, 256, grid, dim3(256), 0, a, o);
     SELLA_LAUNCHB(c, emt_hvp_gather_kernel, emt_hvp_gather_vb, 256, grid, dim3(256), 0, a, o);
@@ -995,12 +936,10 @@ int sella::emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const do
                                 const double* dconst, double rc, double acut, double cutoff, double beta, EmtHvpState* st) {
     EmtArgs a;
     double* ex;                                                       // F2 (n), c_i = g_i . v (n; HVB_W n for a block product)
-    const size_t extra = (size_t)(1 + HVB_W) * n;
-    SCHK(emt_density_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, extra, &a, &ex));
-    SELLA_LAUNCHB(c, emt_f2_kernel, emt_f2_vb, 256, dim3((n + 255) / 256), dim3(256), 0, a, ex);
-    HIPCHK(hipGetLastError());
+    const size_t dots = (size_t)HVB_W * n;
+    SCHK(emt_f2_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, dots, &a, &ex));
     const char* lo = reinterpret_cast<const char*>(a.pos);            // (the positions lead the slot)
-    const char* hi = reinterpret_cast<const char*>(ex + extra);
+    const char* hi = reinterpret_cast<const char*>(ex + n + dots);
     st->own_bytes = (size_t)(hi - lo);
     SCHK(dev_alloc(c, st->own_bytes, &st->own));
     HIPCHK(s_memcpy(c, st->own, lo, st->own_bytes, hipMemcpyDeviceToDevice));

@@ -151,6 +151,10 @@ def test_product_structure(ctx, name):
     assert np.abs(HV[3]).max() <= 1e-10 * np.abs(H).max()              # the cap of the acoustic sums elsewhere
     fixed = at.calc.hessian_vector_product(at, V[2, :n])
     assert np.abs(HV[2, :n] - fixed).max() <= tol
+    if ctx.backend == 'emu':
+        # the position rows are the arithmetic of the product at fixed cell (one gather body, csrc/emt_hessian.hip): bit for
+        # bit where nothing is contracted; on the device the 8- and the 4-vector instantiation may fuse differently
+        assert np.array_equal(HV[2, :n], fixed)
     assert np.array_equal(at.calc.cell_hessian_vector_product(at, V), HV)
 
 
