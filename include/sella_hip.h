@@ -579,9 +579,29 @@ int sella_fd_destroy(sella_fd* fd);
  * vanishing-vector rule: a zero row gives a zero row.
  * The operator must be destroyed before its calculator and context.  SELLA_E_INVALID: a null pointer, n != sella_calc_dim,
  * m <= 0 or m > n with idx given, idx not ascending, an m (sella_hvp_matvec) / n (sella_davidson_hvp) that is not the
- * operator's.                                                                                                            */
+ * operator's.
+ * A second kind of the same operator, for the EMT calculator in a cell run (sella_hvp_create_cell): the analytic Hessian of
+ * positions and cell in the coordinates [x; p], x the n Cartesian coordinates and p the mc parameters of the cell (the masked
+ * log-deformation of CellCartesianPES), resident at the geometry (x0, cell; lattice vectors in the rows of cell).  What the
+ * parametrisation contributes depends on the geometry only and is handed over at creation: J = dC.ravel()/dp (9 x mc,
+ * row-major), G (mc x mc, symmetric: the first derivative dE/dC contracted with the second derivative of C(p)) and, with a
+ * scalar pressure, P = p d2|det C|/dC2 (9 x 9; NULL: none).  For a vector [v_x; v_p]: W = J v_p is the variation of the cell,
+ * [y_x; y_C] the product of the Hessian in [x; C.ravel()] with [v_x; W] (the pair passes of sella_emt_cell_hvp on the
+ * resident state: nothing uploaded, no density pass per product), and y_p = J^T (y_C + P W) + G v_p.  idx selects the mx free
+ * POSITION coordinates (ascending; NULL: all n); the cell parameters are always free and stand behind them, so the
+ * eigensolver's dimension is m = (idx ? mx : n) + mc, and the full dimension (the rows of sella_hvp_pairs) is n + mc:
+ * [vfull_x; v_p] and its product.  Every entry above means on this kind what it means on the first: single products are
+ * recorded, |[v_x; v_p]| < 1e-12 gives a zero product that is counted and not recorded, block products (four rows per
+ * workgroup, a row's result independent of its slot, of the number of rows and of the other rows) are counted and not
+ * recorded, sella_hvp_diag returns diag(H_xx)[idx] followed by the mc diagonal entries of J^T (H_CC + P) J + G (from one
+ * block product of unit rows that is not counted), and both Davidson drivers take it unchanged.  SELLA_E_INVALID: a null
+ * pointer (P excepted), a calculator that is not the EMT kind, n != sella_calc_dim, mc < 1 or mc > 9, idx not ascending or
+ * out of range, a singular cell, a shift of the calculator that is no lattice translation of `cell`.                       */
 typedef struct sella_hvp sella_hvp;
 int sella_hvp_create(sella_calc* calc, int n, const double* x0, const int* idx, int m, sella_hvp** op);
+int sella_hvp_create_cell(sella_calc* calc, int n, const double* x0, const double* cell /* 9 */, const int* idx, int mx,
+                          int mc, const double* J /* 9 x mc */, const double* G /* mc x mc */, const double* P /* 9 x 9 or NULL */,
+                          sella_hvp** op);
 int sella_hvp_matvec(void* op, const double* v, double* Av, int m);
 int sella_hvp_npairs(sella_hvp* op);
 long sella_hvp_calls(sella_hvp* op);

@@ -129,6 +129,8 @@ SIGNATURES = {
     'sella_fd_pairs': (c_int, [c_void_p, c_void_p, c_void_p]),
     'sella_fd_destroy': (c_int, [c_void_p]),
     'sella_hvp_create': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, POINTER(c_void_p)]),
+    'sella_hvp_create_cell': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      POINTER(c_void_p)]),
     'sella_hvp_matvec': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'sella_hvp_npairs': (c_int, [c_void_p]),
     'sella_hvp_calls': (c_long, [c_void_p]),

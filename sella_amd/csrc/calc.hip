@@ -12,7 +12,9 @@
 //                        same selection, on a state built once at x0 and owned by the operator: device vector in, device
 //                        vector out, no host wait per product (the third operator kind of sella_davidson, davidson.hip);
 //                        the pairs are recorded on the device.  Not force calls.  The same for the rows of a device panel
-//                        (hvp_device_apply_block: the operator of sella_davidson_block_hvp; not recorded), and diag(H)
+//                        (hvp_device_apply_block: the operator of sella_davidson_block_hvp; not recorded), and diag(H).
+//                        A second kind (sella_hvp_create_cell, EMT only): the Hessian of positions and cell in the
+//                        coordinates [x; p] of a cell run, through the same entries
 #include "emt.h"
 
 #include <algorithm>
@@ -480,6 +482,11 @@ struct sella_hvp {
     int n = 0, m = 0, ld = 0, nb = 0;     // full dimension, the eigensolver's, row stride, workgroups of the scatter
     bool select = false;
     EmtHvpState emt;                      // EMT kind
+    // the kind of positions and cell (sella_hvp_create_cell): n = nx + mc and m = mx + mc, the mc cell parameters behind the
+    // nx position coordinates (mx of them free: inv covers the positions); nb counts the workgroups of the positions
+    bool cell = false;
+    int nx = 0, mx = 0, mc = 0;
+    EmtCellHvpState cemt;
     double* aux = nullptr;                // part (nb) | x, y of the host entry (ld each) | model: S (nu x ld), t | inv (n ints)
     size_t aux_bytes = 0, chunk_bytes = 0;
     double *part = nullptr, *dx = nullptr, *dy = nullptr, *S = nullptr, *t = nullptr;
@@ -499,11 +506,39 @@ struct sella_hvp {
 static void hvp_release(sella_hvp* o) {
     sella_ctx* c = o->calc->c;
     (void)stream_sync_raw(c);
-    if (o->calc->kind == 1) emt_hvp_state_destroy(c, &o->emt);
+    if (o->cell) emt_hvp_state_destroy(c, &o->cemt.s);
+    else if (o->calc->kind == 1) emt_hvp_state_destroy(c, &o->emt);
     for (double* p : o->chunks) dev_free(c, p, o->chunk_bytes);
     if (o->aux) dev_free(c, o->aux, o->aux_bytes);
     if (o->blk) dev_free(c, o->blk, o->blk_bytes);
     delete o;
+}
+
+// The operator's own device arrays (o->aux; o->n, o->ld set): `nparts` partial sums of |v|^2, the vectors of the host entry,
+// the model kind's rows, and inv over the `ninv` coordinates the m indices idx select (idx null: no inv)
+static int hvp_aux(sella_hvp* o, const int* idx, int m, int ninv, int nparts, int nu) {
+    sella_ctx* c = o->calc->c;
+    const size_t ld = (size_t)o->ld, ldp = (size_t)round_up(nu > 0 ? nu : 1, 8), nbp = (size_t)round_up(nparts, 8);
+    const size_t words = nbp + 2 * ld + (size_t)nu * ld + ldp + (ld + 1) / 2;
+    o->aux_bytes = words * sizeof(double);
+    o->chunk_bytes = ((size_t)2 * HVP_CHUNK * ld + HVP_CHUNK) * sizeof(double);
+    const int st = dev_alloc(c, o->aux_bytes, &o->aux);
+    if (st != SELLA_OK) { o->aux = nullptr; return st; }
+    HIPCHK(s_memset0(c, o->aux, o->aux_bytes));
+    o->part = o->aux; o->dx = o->part + nbp; o->dy = o->dx + ld; o->S = o->dy + ld; o->t = o->S + (size_t)nu * ld;
+    if (idx) {
+        std::vector<int> inv((size_t)ninv, -1);
+        for (int q = 0; q < m; ++q) inv[idx[q]] = q;
+        o->inv = reinterpret_cast<int*>(o->t + ldp);
+        SCHK(h2d_async(c, o->inv, inv.data(), (size_t)ninv * sizeof(int)));
+    }
+    return SELLA_OK;
+}
+
+static bool hvp_ascending(const int* idx, int m, int n) {
+    for (int q = 0; q < m; ++q)
+        if (idx[q] < 0 || idx[q] >= n || (q > 0 && idx[q] <= idx[q - 1])) return false;
+    return true;
 }
 
 extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const int* idx, int m, sella_hvp** out) {
@@ -511,12 +546,10 @@ extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const
         set_error("hvp operator: invalid arguments");
         return SELLA_E_INVALID;
     }
-    if (idx)
-        for (int q = 0; q < m; ++q)
-            if (idx[q] < 0 || idx[q] >= n || (q > 0 && idx[q] <= idx[q - 1])) {
-                set_error("hvp operator: the free coordinates must be ascending indices below %d", n);
-                return SELLA_E_INVALID;
-            }
+    if (idx && !hvp_ascending(idx, m, n)) {
+        set_error("hvp operator: the free coordinates must be ascending indices below %d", n);
+        return SELLA_E_INVALID;
+    }
     sella_ctx* c = calc->c;
     const int nu = calc->kind == 0 ? calc->nu : 0;
     if (calc->kind == 0 && !mat_get(c, calc->A)) {
@@ -527,22 +560,10 @@ extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const
     o->calc = calc; o->n = n; o->m = idx ? m : n; o->select = idx != nullptr;
     o->ld = round_up(n, 8);
     o->nb = (n + 255) / 256;
-    const size_t ld = (size_t)o->ld, ldp = (size_t)round_up(nu > 0 ? nu : 1, 8), nbp = (size_t)round_up(o->nb, 8);
-    const size_t words = nbp + 2 * ld + (size_t)nu * ld + ldp + (ld + 1) / 2;
-    o->aux_bytes = words * sizeof(double);
-    o->chunk_bytes = ((size_t)2 * HVP_CHUNK * ld + HVP_CHUNK) * sizeof(double);
     auto fail = [&](int st) { hvp_release(o); return st; };
-    int st = dev_alloc(c, o->aux_bytes, &o->aux);
-    if (st != SELLA_OK) { o->aux = nullptr; return fail(st); }
-    if (s_memset0(c, o->aux, o->aux_bytes) != hipSuccess) return fail(SELLA_E_HIP);
-    o->part = o->aux; o->dx = o->part + nbp; o->dy = o->dx + ld; o->S = o->dy + ld; o->t = o->S + (size_t)nu * ld;
-    if (idx) {
-        std::vector<int> inv((size_t)n, -1);
-        for (int q = 0; q < m; ++q) inv[idx[q]] = q;
-        o->inv = reinterpret_cast<int*>(o->t + ldp);
-        st = h2d_async(c, o->inv, inv.data(), (size_t)n * sizeof(int));
-        if (st != SELLA_OK) return fail(st);
-    }
+    int st = hvp_aux(o, idx, m, n, o->nb, nu);
+    if (st != SELLA_OK) return fail(st);
+    const size_t ld = (size_t)o->ld;
     if (calc->kind == 1) {
         st = emt_hvp_state_create(c, calc->natoms, x0, calc->par.data(), calc->nshift, calc->shifts.data(), calc->dconst, calc->rc,
                                   calc->acut, calc->cutoff, calc->beta, &o->emt);
@@ -560,6 +581,43 @@ extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const
         if (st == SELLA_OK) st = stream_wait(c);
     }
     if (st != SELLA_OK) return fail(st);
+    *out = o;
+    return SELLA_OK;
+}
+
+// The Hessian of positions and cell in the coordinates [x; p] of a cell run (emt_hessian.hip, the resident operator of
+// positions and cell): n position coordinates at x0 in `cell` (lattice vectors in its rows), mc cell parameters with
+// dC/dp = J (9 x mc), the curvature G (mc x mc, symmetric) of the parametrisation and P (9 x 9) of a pressure (NULL: none).
+// idx: the mx free POSITION coordinates; the cell parameters are always free and stand behind them.
+extern "C" int sella_hvp_create_cell(sella_calc* calc, int n, const double* x0, const double* cell, const int* idx, int mx, int mc,
+                                     const double* J, const double* G, const double* P, sella_hvp** out) {
+    if (!calc || !out || !x0 || !cell || !J || !G || n <= 0 || calc->n != n || (idx && (mx < 0 || mx > n))) {
+        set_error("hvp cell operator: invalid arguments");
+        return SELLA_E_INVALID;
+    }
+    if (calc->kind != 1) {
+        set_error("hvp cell operator: only the EMT calculator has second derivatives with respect to the cell");
+        return SELLA_E_INVALID;
+    }
+    if (mc < 1 || mc > 9) {
+        set_error("hvp cell operator: 1 to 9 cell parameters, not %d", mc);
+        return SELLA_E_INVALID;
+    }
+    if (idx && !hvp_ascending(idx, mx, n)) {
+        set_error("hvp cell operator: the free coordinates must be ascending indices below %d", n);
+        return SELLA_E_INVALID;
+    }
+    sella_ctx* c = calc->c;
+    sella_hvp* o = new sella_hvp();
+    o->calc = calc; o->cell = true; o->select = idx != nullptr;
+    o->nx = n; o->mx = idx ? mx : n; o->mc = mc;
+    o->n = n + mc; o->m = o->mx + mc;
+    o->ld = round_up(o->n, 8);
+    o->nb = (n + 255) / 256;
+    int st = emt_chvp_state_create(c, calc->natoms, x0, cell, calc->par.data(), calc->nshift, calc->shifts.data(), calc->dconst,
+                                   calc->rc, calc->acut, calc->cutoff, calc->beta, mc, J, G, P, &o->cemt);
+    if (st == SELLA_OK) st = hvp_aux(o, idx, mx, n, o->nb + 1, 0);
+    if (st != SELLA_OK) { hvp_release(o); return st; }
     *out = o;
     return SELLA_OK;
 }
@@ -582,6 +640,10 @@ int sella::hvp_device_apply(sella_hvp* o, const double* x, double* y) {
     int* flag = reinterpret_cast<int*>(base + (size_t)2 * HVP_CHUNK * ld) + r;
     ++o->calls;
     ++o->nrec;
+    if (o->cell) {
+        const EmtCellHvpIO io = {x, 0, y, 0, o->inv, o->mx, v, 0, hv, o->part, flag};
+        return emt_chvp_state_apply(c, o->cemt, io);
+    }
     const int n = o->n;
     SELLA_LAUNCHB(c, hvp_scatter_kernel, hvp_scatter_vb, 256, dim3(o->nb), dim3(256), 0, n, x, (const int*)o->inv, v, o->part);
     if (k->kind == 1) return emt_hvp_state_apply(c, o->emt, v, hv, o->part, o->nb, o->inv, y, flag);
@@ -620,6 +682,12 @@ static int hvp_block_buffers(sella_hvp* o) {
     return SELLA_OK;
 }
 
+// the kind of positions and cell: the rows are spread into the staging panel (the kernels need T = n_s W of every row anyway)
+static int hvp_cell_block(sella_hvp* o, const double* X, int ldx, int nh, double* Y, int ldy) {
+    const EmtCellHvpIO io = {X, ldx, Y, ldy, o->inv, o->mx, o->bstage, o->ld, nullptr, nullptr, nullptr};
+    return emt_chvp_state_apply_block(o->calc->c, o->cemt, io, nh);
+}
+
 // Y[h] = (H vfull_h)[free] for the nh <= 16 rows of the device panel X (m entries each, rows ldx / ldy apart), vfull_h zero on
 // the pinned coordinates: queued on the context's stream, nothing waited for, nothing copied.  nh calls; not entered in the
 // pair record (that belongs to the secant update of PES.diag), and no vanishing-vector rule: a zero row gives a zero row.
@@ -644,6 +712,7 @@ int sella::hvp_device_apply_block(sella_hvp* o, const double* X, int ldx, int nh
         }
     }
     o->calls += nh;
+    if (o->cell) return hvp_cell_block(o, X, ldx, nh, Y, ldy);
     const double* V = X;
     int ldv = ldx;
     if (o->inv || (k->kind == 0 && ldx != o->ld)) {
@@ -693,6 +762,23 @@ extern "C" int sella_hvp_diag(sella_hvp* o, double* diag) {
     }
     sella_calc* k = o->calc;
     sella_ctx* c = k->c;
+    if (o->cell) {
+        // the positions from emt_hdiag; the cell entries from one block product of the mc unit rows (not counted): one upload
+        // of the rows, one read-back of the mc x mc block behind the positions
+        SCHK(emt_hvp_state_diag(c, o->cemt.s, o->inv, o->dy));
+        SCHK(hvp_block_buffers(o));
+        const size_t ldm = (size_t)o->ldm, mx = (size_t)o->mx, mc = (size_t)o->mc;
+        std::vector<double> rows(mc * ldm, 0.0);
+        for (size_t h = 0; h < mc; ++h) rows[h * ldm + mx + h] = 1.0;
+        SCHK(h2d_async(c, o->bx, rows.data(), rows.size() * sizeof(double)));
+        SCHK(hvp_cell_block(o, o->bx, o->ldm, o->mc, o->by, o->ldm));
+        double pp[81];
+        SCHK(d2h_async(c, diag, o->dy, mx * sizeof(double)));
+        SCHK(d2h_async_2d(c, pp, o->by + mx, ldm * sizeof(double), mc * sizeof(double), mc));
+        SCHK(stream_wait(c));
+        for (size_t h = 0; h < mc; ++h) diag[mx + h] = pp[h * mc + h];
+        return SELLA_OK;
+    }
     if (k->kind == 1) {
         SCHK(emt_hvp_state_diag(c, o->emt, o->inv, o->dy));
     } else {

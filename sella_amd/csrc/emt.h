@@ -79,4 +79,32 @@ int emt_hvp_state_apply_block(sella_ctx* c, const EmtHvpState& st, const double*
                               int ldy);
 int emt_hvp_state_diag(sella_ctx* c, const EmtHvpState& st, const int* inv, double* y);
 
+// The same state for the operator of positions and cell (calc.hip, sella_hvp_create_cell): the product in the coordinates
+// [x; p], p the mc cell parameters, W = J v_p the variation of the cell.  Behind what EmtHvpState keeps, in the same
+// allocation: the image indices n_s, J (9 x mc), G (mc x mc), P (9 x 9, zero without a pressure), and per vector of a
+// block of 16 (a single product uses slot 0) the table T[s] = n_s W, [W; v_p] and the per-atom shares of the nine cell rows.
+struct EmtCellHvpState {
+    EmtHvpState s;
+    int mc = 0;
+    double *nimg = nullptr, *J = nullptr, *G = nullptr, *P = nullptr;
+    double *T = nullptr, *wv = nullptr, *share = nullptr;    // (16, nshift, 3); (16, 18): W then v_p; (16, n, 9)
+};
+// what a product reads and writes besides the state: the eigensolver's vectors X (row h at X + h ldx: mx free position
+// entries, then mc cell entries; inv as above, over the 3n position coordinates) and products Y, and the full-length rows
+// (3n position entries, then mc) the vectors are spread into (vfull) and, for a single product, the product is recorded in
+// (hvfull; null for a block).  part: 3n / 256 (rounded up) + 1 partial sums of |v|^2 and flag, for a single product only.
+struct EmtCellHvpIO {
+    const double* X; int ldx;
+    double* Y; int ldy;
+    const int* inv; int mx;
+    double* vfull; int ldv;
+    double* hvfull;
+    double* part; int* flag;
+};
+int emt_chvp_state_create(sella_ctx* c, int n, const double* pos, const double* cell, const double* par, int nshift,
+                          const double* shifts, const double* dconst, double rc, double acut, double cutoff, double beta, int mc,
+                          const double* J, const double* G, const double* P, EmtCellHvpState* st);
+int emt_chvp_state_apply(sella_ctx* c, const EmtCellHvpState& st, const EmtCellHvpIO& io);
+int emt_chvp_state_apply_block(sella_ctx* c, const EmtCellHvpState& st, const EmtCellHvpIO& io, int nh);
+
 }  // namespace sella

@@ -239,7 +239,8 @@ __global__ __launch_bounds__(256) void emt_hess_pair_kernel(EmtArgs a, EmtHessOu
 //   load(q, j, x)           x = row of atom j in vector q
 //   c(q, j)                 where the dot c_j of vector q lives
 //   P::Terms                the arithmetic of one vector in one visit, contracted or not (below)
-// The arithmetic of one vector in a visit, d the displacement of the pair by the vector.  It stands twice because `#pragma
+// The arithmetic of one vector in a visit, d the displacement of the pair by the vector (row: the position rows; cell: the
+// nine cell sums of a CELL description).  It stands twice because `#pragma
 // clang fp contract` is lexical and no template can switch it: EmtTerms leaves the contraction into fused multiply-adds to
 // the compiler, EmtTermsExact rounds every product on its own (the panel of the block product: see there).
 struct EmtTerms {
@@ -253,6 +254,18 @@ struct EmtTerms {
         acc[0] += c1 * d[0] + along * p.ux;
         acc[1] += c1 * d[1] + along * p.uy;
         acc[2] += c1 * d[2] + along * p.uz;
+    }
+    // CELL: acc9[3 k + b] += n_k [fi w'_ij u_b - 1/2 (K d)_b], the atom's share of the nine cell rows
+    static __device__ __forceinline__ void cell(const EmtPair& p, double c1, double c2, const double d[3], double fi,
+                                                const double nv[3], double* acc9) {
+        const double u[3] = {p.ux, p.uy, p.uz};
+        const double along = c2 * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]), own = fi * p.wp_ij;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const double tb = own * u[b] - 0.5 * (c1 * d[b] + along * u[b]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc9[3 * k + b] += nv[k] * tb;
+        }
     }
 };
 struct EmtTermsExact {
@@ -271,6 +284,21 @@ struct EmtTermsExact {
         acc[0] += c1 * d[0] + along * p.ux;
         acc[1] += c1 * d[1] + along * p.uy;
         acc[2] += c1 * d[2] + along * p.uz;
+    }
+    // CELL: acc9[3 k + b] += n_k [fi w'_ij u_b - 1/2 (K d)_b], the atom's share of the nine cell rows
+    static __device__ __forceinline__ void cell(const EmtPair& p, double c1, double c2, const double d[3], double fi,
+                                                const double nv[3], double* acc9) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+        const double u[3] = {p.ux, p.uy, p.uz};
+        const double along = c2 * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]), own = fi * p.wp_ij;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) {
+            const double tb = own * u[b] - 0.5 * (c1 * d[b] + along * u[b]);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc9[3 * k + b] += nv[k] * tb;
+        }
     }
 };
 
@@ -357,16 +385,7 @@ __device__ __forceinline__ void emt_gather_body(const VB vb, const EmtArgs& a, c
                 for (int b = 0; b < 3; ++b) d[b] -= T[b];
             }
             if (!P::CELL || p.j != i) P::Terms::row(p, c1, c2, d, fc[q], f2j * o.c(q, p.j), acc[q]);   // an own image moves no position block
-            if constexpr (P::CELL) {
-                const double u[3] = {p.ux, p.uy, p.uz};
-                const double along = c2 * (p.ux * d[0] + p.uy * d[1] + p.uz * d[2]), own = fc[q] * p.wp_ij;
-#pragma unroll
-                for (int b = 0; b < 3; ++b) {
-                    const double tb = own * u[b] - 0.5 * (c1 * d[b] + along * u[b]);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) acc[q][3 + 3 * k + b] += nv[k] * tb;
-                }
-            }
+            if constexpr (P::CELL) P::Terms::cell(p, c1, c2, d, fc[q], nv, acc[q] + 3);
         }
     };
     emt_by_image<false>(a, i, &incomplete, visit);
@@ -729,6 +748,184 @@ __device__ __forceinline__ void emt_chvp_finish_vb(const VB vb, int n, EmtCellHv
 }
 __global__ __launch_bounds__(256) void emt_chvp_finish_kernel(int n, EmtCellHvp o) { emt_chvp_finish_vb(vb_hw(), n, o); }
 
+// ---- the resident operator of positions and cell (calc.hip, sella_hvp_create_cell) -------------------------------------------
+// The product above in the coordinates [x; p] of a cell run (p: mc parameters of the cell, W = J p its variation), on a state
+// that stays on the device (EmtCellHvpState) and on device vectors: y_x as above with T[s] = n_s W, y_p = J^T (y_C + P W) + G p.
+// Four stages, for ONE vector (it is recorded, |v| < 1e-12 gives zero and flag 0) or for the nh <= HVB_W rows of a panel:
+//   emt_chvpo_scatter   row h = vb.y: the free position entries into the full-length row, |v|^2 in partial sums (the cell
+//                       entries included); the workgroup behind those of the positions forms W = J v_p and T[s] = n_s W and
+//                       puts v_p into the full-length row
+//   dots, gather        emt_dots_body / emt_gather_body with CELL: emt_chvpo1_* one vector per workgroup, emt_chvpob_*
+//                       CHVP_KQ rows of the panel per workgroup on a grid (n, ceil(nh / CHVP_KQ)), every product rounded on its
+//                       own (EmtTermsExact) like the block at fixed cell: a row's result does not depend on its slot, on nh or
+//                       on the other rows.  Position rows go to Y (and the record), the nine cell sums to the share array.
+//   emt_chvpo_finish    row h = vb.x: y_C = sum_i s_i in the order of emt_chvp_finish, + P W, y_p = J^T y_C + G v_p
+// Scatter and finish are the same kernels for one vector and for a panel.
+struct EmtCellOp {
+    const double* F2;
+    const double *nimg, *J, *G, *P;         // n_s (nshift x 3), 9 x mc, mc x mc, 9 x 9
+    int mc, nshift;
+    double *T, *wv, *share, *cdot;          // (HVB_W, nshift, 3); (HVB_W, 18): W, v_p; (HVB_W, n, 9); n (one vector) or n x HVB_W
+    const double* X; int ldx;               // the eigensolver's vectors: mx free position entries, then mc
+    double* Y; int ldy;
+    const int* inv; int mx;                 // position coordinate -> entry of X, -1 if pinned; null: all free
+    double* vfull; int ldv;                 // full-length rows: 3n position entries, then mc
+    double* hvfull;                         // one vector: the product in full length (the pair record)
+    const double* partc; double* part; int nb;    // one vector: nb + 1 partial sums of |v|^2 (nb = workgroups of the positions)
+    int* flag;
+    int nh;
+};
+
+__device__ __forceinline__ void emt_chvpo_scatter_vb(const VB vb, int n3, EmtCellOp o) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    __shared__ double red[4];
+    __shared__ double Wl[9];
+    const int h = vb.y, t = threadIdx.x;
+    const double* x = o.X + (size_t)h * o.ldx;
+    double* vf = o.vfull + (size_t)h * o.ldv;
+    double v = 0.0;
+    if ((int)vb.x < o.nb) {
+        const int p = vb.x * 256 + t;
+        if (p < n3) {
+            const int q = o.inv ? o.inv[p] : p;
+            if (q >= 0) v = x[q];
+            vf[p] = v;
+        }
+    } else if (t < o.mc) {
+        v = x[o.mx + t];
+        vf[n3 + t] = v;
+        o.wv[h * 18 + 9 + t] = v;
+    }
+    if (o.part) {
+        const double s = block_sum(v * v, red);
+        if (t == 0) o.part[vb.x] = s;
+    }
+    if ((int)vb.x < o.nb) return;
+    if (t < 9) {
+        double w = 0.0;
+        for (int c = 0; c < o.mc; ++c) w += o.J[t * o.mc + c] * x[o.mx + c];
+        Wl[t] = w;
+        o.wv[h * 18 + t] = w;
+    }
+    __syncthreads();
+    double* T = o.T + (size_t)h * o.nshift * 3;
+    for (int s = t; s < o.nshift; s += 256) {
+        const double* ns = o.nimg + 3 * s;
+#pragma unroll
+        for (int b = 0; b < 3; ++b) T[3 * s + b] = ns[0] * Wl[b] + ns[1] * Wl[3 + b] + ns[2] * Wl[6 + b];
+    }
+}
+__global__ __launch_bounds__(256) void emt_chvpo_scatter_kernel(int n3, EmtCellOp o) { emt_chvpo_scatter_vb(vb_hw(), n3, o); }
+
+__device__ __forceinline__ EmtRows<1, true> emt_rows1(const EmtArgs& a, const EmtCellOp& o) {
+    return {o.vfull, 0, o.cdot, a.n, 0, o.nimg, o.T, o.nshift};
+}
+__device__ __forceinline__ void emt_chvpo1_dots_vb(const VB vb, EmtArgs a, EmtCellOp o) { emt_dots_body(vb, a, emt_rows1(a, o)); }
+__global__ __launch_bounds__(256) void emt_chvpo1_dots_kernel(EmtArgs a, EmtCellOp o) { emt_chvpo1_dots_vb(vb_hw(), a, o); }
+
+// whether the vector of a single product counts (|v| >= 1e-12), from the partial sums of the scatter
+__device__ __forceinline__ bool emt_chvpo_live(const EmtCellOp& o, double* red) {
+    double s = 0.0;
+    for (int b = threadIdx.x; b < o.nb + 1; b += 256) s += o.partc[b];
+    s = block_sum(s, red);
+    return !(sqrt(s) < 1e-12);
+}
+
+__device__ __forceinline__ void emt_chvpo1_gather_vb(const VB vb, EmtArgs a, EmtCellOp o) {
+    __shared__ double red1[4];
+    const bool live = emt_chvpo_live(o, red1);
+    emt_gather_body(vb, a, o.F2, emt_rows1(a, o), [&](int, int c, double v) {
+        if (c < 3) {
+            const int p = 3 * vb.x + c, q = o.inv ? o.inv[p] : p;
+            const double h = live ? v : 0.0;
+            o.hvfull[p] = h;
+            if (q >= 0) o.Y[q] = h;
+        } else {
+            o.share[(size_t)vb.x * 9 + (c - 3)] = v;
+        }
+    });
+}
+__global__ __launch_bounds__(256) void emt_chvpo1_gather_kernel(EmtArgs a, EmtCellOp o) { emt_chvpo1_gather_vb(vb_hw(), a, o); }
+
+// rows q0 .. q0 + CHVP_KQ - 1 of the panel; rows beyond nh are never read (their slots repeat row nh - 1 and are not stored)
+struct EmtCellHvpB {
+    using Terms = EmtTermsExact;
+    static constexpr int W = CHVP_KQ;
+    static constexpr bool CELL = true;
+    const double* V; int ldv;
+    int nh, q0;
+    double* cdot;                           // n x HVB_W: c_j of row r at [HVB_W j + r]
+    const double* nimg; const double* T; int nshift;
+    __device__ __forceinline__ int row(int q) const { return q0 + q < nh ? q0 + q : nh - 1; }
+    __device__ __forceinline__ void load(int q, int j, double x[3]) const {
+        const double* v = V + (size_t)row(q) * ldv + 3 * j;
+        x[0] = v[0]; x[1] = v[1]; x[2] = v[2];
+    }
+    __device__ __forceinline__ double& c(int q, int j) const { return cdot[(size_t)j * HVB_W + q0 + q]; }
+    __device__ __forceinline__ const double* shift(int q, int s) const { return T + ((size_t)row(q) * nshift + s) * 3; }
+};
+__device__ __forceinline__ EmtCellHvpB emt_rowsb(const VB vb, const EmtCellOp& o) {
+    return {o.vfull, o.ldv, o.nh, (int)vb.y * CHVP_KQ, o.cdot, o.nimg, o.T, o.nshift};
+}
+__device__ __forceinline__ void emt_chvpob_dots_vb(const VB vb, EmtArgs a, EmtCellOp o) { emt_dots_body(vb, a, emt_rowsb(vb, o)); }
+__global__ __launch_bounds__(256) void emt_chvpob_dots_kernel(EmtArgs a, EmtCellOp o) { emt_chvpob_dots_vb(vb_hw(), a, o); }
+
+__device__ __forceinline__ void emt_chvpob_gather_vb(const VB vb, EmtArgs a, EmtCellOp o) {
+    const auto rows = emt_rowsb(vb, o);
+    emt_gather_body(vb, a, o.F2, rows, [&](int q, int c, double v) {
+        const int h = rows.q0 + q;
+        if (h >= o.nh) return;
+        if (c < 3) {
+            const int p = 3 * vb.x + c, r = o.inv ? o.inv[p] : p;
+            if (r >= 0) o.Y[(size_t)h * o.ldy + r] = v;
+        } else {
+            o.share[((size_t)h * a.n + vb.x) * 9 + (c - 3)] = v;
+        }
+    });
+}
+__global__ __launch_bounds__(256) void emt_chvpob_gather_kernel(EmtArgs a, EmtCellOp o) { emt_chvpob_gather_vb(vb_hw(), a, o); }
+
+__device__ __forceinline__ void emt_chvpo_finish_vb(const VB vb, int n, EmtCellOp o) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    __shared__ double part[4][9];
+    __shared__ double red1[4];
+    __shared__ double yC[9];
+    const int h = vb.x, t = threadIdx.x;
+    const bool live = o.partc ? emt_chvpo_live(o, red1) : true;
+    double acc[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) acc[c] = 0.0;
+    for (int i = t; i < n; i += 256) {
+        const double* s = o.share + ((size_t)h * n + i) * 9;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) acc[c] += s[c];
+    }
+#pragma unroll
+    for (int c = 0; c < 9; ++c) block_put<9>(part, c, acc[c]);
+    __syncthreads();
+    const double* w = o.wv + h * 18;
+    if (t < 9) {
+        double y = block_total<9>(part, t);
+        for (int u = 0; u < 9; ++u) y += o.P[t * 9 + u] * w[u];
+        yC[t] = y;
+    }
+    __syncthreads();
+    if (t < o.mc) {
+        double y = 0.0;
+        for (int r = 0; r < 9; ++r) y += o.J[r * o.mc + t] * yC[r];
+        for (int c = 0; c < o.mc; ++c) y += o.G[t * o.mc + c] * w[9 + c];
+        if (!live) y = 0.0;
+        if (o.hvfull) o.hvfull[3 * n + t] = y;
+        o.Y[(size_t)h * o.ldy + o.mx + t] = y;
+    }
+    if (o.flag && t == 0) *o.flag = live ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void emt_chvpo_finish_kernel(int n, EmtCellOp o) { emt_chvpo_finish_vb(vb_hw(), n, o); }
+
 struct TempMats {                           // device matrices of one call, back to the pool on every way out (stream-ordered)
     sella_ctx* c;
     sella_mat h[3] = {SELLA_NO_MAT, SELLA_NO_MAT, SELLA_NO_MAT};
@@ -932,17 +1129,19 @@ int sella::emt_hvp_resident(sella_ctx* c, int n, const double* pos, const double
 // One density pass and one emt_f2 at `pos`; what they leave in scratch slot SCR_MISC0 (positions, sigma1, dEdsig, the
 // lists, F2 — and the parameter table and shifts unless `dconst` holds them) is copied into an allocation of the state's
 // own, because the next force call reuses the slot.
-int sella::emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
-                                const double* dconst, double rc, double acut, double cutoff, double beta, EmtHvpState* st) {
+// `room` more doubles of the state's own behind them at *behind (contents undefined).
+static int emt_hvp_state_create_room(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                                     const double* dconst, double rc, double acut, double cutoff, double beta, size_t room,
+                                     EmtHvpState* st, double** behind) {
     EmtArgs a;
     double* ex;                                                       // F2 (n), c_i = g_i . v (n; HVB_W n for a block product)
     const size_t dots = (size_t)HVB_W * n;
     SCHK(emt_f2_queue(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, dots, &a, &ex));
     const char* lo = reinterpret_cast<const char*>(a.pos);            // (the positions lead the slot)
     const char* hi = reinterpret_cast<const char*>(ex + n + dots);
-    st->own_bytes = (size_t)(hi - lo);
+    st->own_bytes = (size_t)(hi - lo) + room * sizeof(double);
     SCHK(dev_alloc(c, st->own_bytes, &st->own));
-    HIPCHK(s_memcpy(c, st->own, lo, st->own_bytes, hipMemcpyDeviceToDevice));
+    HIPCHK(s_memcpy(c, st->own, lo, (size_t)(hi - lo), hipMemcpyDeviceToDevice));
     char* base = reinterpret_cast<char*>(st->own);
     auto moved = [&](auto*& p) {                                      // pointers into the slot follow the copy
         const char* q = reinterpret_cast<const char*>(p);
@@ -955,7 +1154,13 @@ int sella::emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const do
     st->a = a;
     st->F2 = ex;
     st->cdot = ex + n;
+    if (behind) *behind = ex + n + dots;
     return stream_wait(c);
+}
+
+int sella::emt_hvp_state_create(sella_ctx* c, int n, const double* pos, const double* par, int nshift, const double* shifts,
+                                const double* dconst, double rc, double acut, double cutoff, double beta, EmtHvpState* st) {
+    return emt_hvp_state_create_room(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta, 0, st, nullptr);
 }
 
 void sella::emt_hvp_state_destroy(sella_ctx* c, EmtHvpState* st) {
@@ -993,6 +1198,63 @@ int sella::emt_hvp_state_apply_block(sella_ctx* c, const EmtHvpState& st, const 
 // y = diag(H)[free] on the device: one launch, nothing waited for
 int sella::emt_hvp_state_diag(sella_ctx* c, const EmtHvpState& st, const int* inv, double* y) {
     SELLA_LAUNCHB(c, emt_hdiag_kernel, emt_hdiag_vb, 256, dim3(st.a.n), dim3(256), 0, st.a, (const double*)st.F2, inv, y);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
+// ---- the resident state of the operator of positions and cell (emt.h) ---------------------------------------------------
+// SELLA_E_INVALID before anything is queued: a singular cell, shifts that are no lattice translations of it.
+int sella::emt_chvp_state_create(sella_ctx* c, int n, const double* pos, const double* cell, const double* par, int nshift,
+                                 const double* shifts, const double* dconst, double rc, double acut, double cutoff, double beta,
+                                 int mc, const double* J, const double* G, const double* P, EmtCellHvpState* st) {
+    std::vector<double> fix;                                          // n_s, J, G, P as they lie on the device
+    SCHK(emt_image_indices(cell, nshift, shifts, fix));
+    const size_t nT = (size_t)3 * nshift, nfix = nT + (size_t)9 * mc + (size_t)mc * mc + 81;
+    fix.insert(fix.end(), J, J + 9 * mc);
+    fix.insert(fix.end(), G, G + mc * mc);
+    if (P) fix.insert(fix.end(), P, P + 81);
+    else fix.insert(fix.end(), 81, 0.0);
+    double* room;
+    SCHK(emt_hvp_state_create_room(c, n, pos, par, nshift, shifts, dconst, rc, acut, cutoff, beta,
+                                   nfix + (size_t)HVB_W * (nT + 18 + (size_t)9 * n), &st->s, &room));
+    st->mc = mc;
+    st->nimg = room; st->J = st->nimg + nT; st->G = st->J + 9 * mc; st->P = st->G + mc * mc;
+    st->T = room + nfix; st->wv = st->T + HVB_W * nT; st->share = st->wv + HVB_W * 18;
+    SCHK(h2d_async(c, room, fix.data(), nfix * sizeof(double)));
+    return stream_wait(c);
+}
+
+static EmtCellOp emt_cell_op(const EmtCellHvpState& st, const EmtCellHvpIO& io, int nh) {
+    EmtCellOp o;
+    o.F2 = st.s.F2; o.nimg = st.nimg; o.J = st.J; o.G = st.G; o.P = st.P; o.mc = st.mc; o.nshift = st.s.a.nshift;
+    o.T = st.T; o.wv = st.wv; o.share = st.share; o.cdot = st.s.cdot;
+    o.X = io.X; o.ldx = io.ldx; o.Y = io.Y; o.ldy = io.ldy; o.inv = io.inv; o.mx = io.mx;
+    o.vfull = io.vfull; o.ldv = io.ldv; o.hvfull = io.hvfull; o.partc = io.part; o.part = io.part;
+    o.nb = (3 * st.s.a.n + 255) / 256; o.flag = io.flag; o.nh = nh;
+    return o;
+}
+
+// one vector: four launches on the context's stream, nothing copied, nothing waited for
+int sella::emt_chvp_state_apply(sella_ctx* c, const EmtCellHvpState& st, const EmtCellHvpIO& io) {
+    const EmtCellOp o = emt_cell_op(st, io, 1);
+    const int n = st.s.a.n;
+    SELLA_LAUNCHB(c, emt_chvpo_scatter_kernel, emt_chvpo_scatter_vb, 256, dim3(o.nb + 1, 1), dim3(256), 0, 3 * n, o);
+    SELLA_LAUNCHB(c, emt_chvpo1_dots_kernel, emt_chvpo1_dots_vb, 256, dim3(n), dim3(256), 0, st.s.a, o);
+    SELLA_LAUNCHB(c, emt_chvpo1_gather_kernel, emt_chvpo1_gather_vb, 256, dim3(n), dim3(256), 0, st.s.a, o);
+    SELLA_LAUNCHB(c, emt_chvpo_finish_kernel, emt_chvpo_finish_vb, 256, dim3(1), dim3(256), 0, n, o);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
+// the nh <= HVB_W rows of a panel: the same four stages, CHVP_KQ rows per workgroup in the two pair passes
+int sella::emt_chvp_state_apply_block(sella_ctx* c, const EmtCellHvpState& st, const EmtCellHvpIO& io, int nh) {
+    const EmtCellOp o = emt_cell_op(st, io, nh);
+    const int n = st.s.a.n;
+    const dim3 grid(n, (unsigned)((nh + CHVP_KQ - 1) / CHVP_KQ));
+    SELLA_LAUNCHB(c, emt_chvpo_scatter_kernel, emt_chvpo_scatter_vb, 256, dim3(o.nb + 1, nh), dim3(256), 0, 3 * n, o);
+    SELLA_LAUNCHB(c, emt_chvpob_dots_kernel, emt_chvpob_dots_vb, 256, grid, dim3(256), 0, st.s.a, o);
+    SELLA_LAUNCHB(c, emt_chvpob_gather_kernel, emt_chvpob_gather_vb, 256, grid, dim3(256), 0, st.s.a, o);
+    SELLA_LAUNCHB(c, emt_chvpo_finish_kernel, emt_chvpo_finish_vb, 256, dim3(nh), dim3(256), 0, n, o);
     HIPCHK(hipGetLastError());
     return SELLA_OK;
 }

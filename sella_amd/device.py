@@ -826,21 +826,47 @@ class DeviceHvpOperator:
     `diagonal()` the diagonal; `Vs` / `AVs` afterwards hold the recorded pairs of the single products (full space, one
     column per product of a non-vanishing vector), like `DeviceFdOperator`.  `through_host=True`
     makes `Context.davidson` run the unchanged `sella_davidson` with `sella_hvp_matvec` as its host callback instead (same
-    results; for comparisons and measurements)."""
+    results; for comparisons and measurements).
 
-    def __init__(self, calc, x0, free=None, through_host=False):
+    `for_cell` makes the second kind (`sella_hvp_create_cell`, device `EMT` only): the Hessian of positions and cell in the
+    coordinates [x; p] of `CellCartesianPES`, with the same methods; its vectors carry the cell parameters behind the free
+    position coordinates."""
+
+    def __init__(self, calc, x0, free=None, through_host=False, _cell=None):
         self.through_host = bool(through_host)
         x0 = as_f64(x0).ravel()
-        self.calc, self.ntrue = calc, x0.size
+        self.calc = calc
         self._free = None if free is None else np.ascontiguousarray(free, dtype=np.int32)
-        n = self.ntrue if self._free is None else len(self._free)
-        self.shape = (n, n)
+        n = x0.size if self._free is None else len(self._free)
+        free_ptr = None if self._free is None else self._free.ctypes.data_as(c_void_p)
+        nfree = 0 if self._free is None else len(self._free)
         h = c_void_p()
-        check(_lib.lib().sella_hvp_create(calc._h, self.ntrue, ptr(x0),
-                                          None if self._free is None else self._free.ctypes.data_as(c_void_p),
-                                          0 if self._free is None else len(self._free), byref(h)))
+        if _cell is None:
+            self.ntrue = x0.size
+            check(_lib.lib().sella_hvp_create(calc._h, x0.size, ptr(x0), free_ptr, nfree, byref(h)))
+        else:
+            cell, J, G, P = _cell
+            cell, J, G = as_f64(cell, (3, 3)), np.ascontiguousarray(as_f64(J)), np.ascontiguousarray(as_f64(G))
+            mc = J.shape[1] if J.ndim == 2 else -1
+            if J.ndim != 2 or J.shape[0] != 9 or G.shape != (mc, mc):
+                raise ValueError(f'expected J of shape (9, mc) and G of shape (mc, mc), got {J.shape} and {G.shape}')
+            P = None if P is None else np.ascontiguousarray(as_f64(P, (9, 9)))
+            self.ntrue = x0.size + mc
+            n += mc
+            check(_lib.lib().sella_hvp_create_cell(calc._h, x0.size, ptr(x0), ptr(cell), free_ptr, nfree, mc, ptr(J), ptr(G),
+                                                   ptr(P), byref(h)))
+        self.shape = (n, n)
         self._h = h
         self._fin = calc.ctx.child(weakref.finalize(self, _lib.lib().sella_hvp_destroy, h))
+
+    @classmethod
+    def for_cell(cls, calc, x0, cell, J, G, P=None, free=None, through_host=False):
+        """The operator of positions and cell at the geometry (x0, cell; lattice vectors in the rows of cell) of an EMT
+        `DeviceCalculator` whose image translations belong to that cell.  J (9, mc) = dC.ravel()/dp, G (mc, mc) symmetric and
+        P (9, 9) or None as `CellCartesianPES._cell_param_maps` gives them (G = (G0 + G0^T) / 2): for [v_x; v_p] the product
+        is [y_x; J^T (y_C + P W) + G v_p] with W = J v_p and [y_x; y_C] the product in [x; C.ravel()].  `free`: the free
+        POSITION coordinates (ascending; None: all); `shape` = (m, m) with m = free positions + mc, `ntrue` = 3N + mc."""
+        return cls(calc, x0, free=free, through_host=through_host, _cell=(cell, J, G, P))
 
     def callback(self):
         """`sella_hvp_matvec` as the `sella_matvec_fn` of the unchanged `sella_davidson` (host vectors per product)."""

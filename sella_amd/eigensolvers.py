@@ -254,7 +254,7 @@ def _free_coordinates(atoms, constraints, free):
 
 
 def lowest_modes(atoms, nev=1, constraints=None, free=None, tol=1e-8, block=None, maxiter=500, maxvec=0, V0=None,
-                 allow_unconverged=False):
+                 allow_unconverged=False, cell=False, cell_mask=None, exp_cell_factor=None, scalar_pressure=0.0):
     """The `nev` lowest curvatures and modes of the Hessian of `atoms` over its free coordinates, without the 3N x 3N
     matrix: block Davidson (`sella_davidson_block_hvp`) on the analytic Hessian-vector operator of a calculator that lives
     in the library (device `EMT`, `QuadraticCubicModel` with a device matrix), preconditioned with the operator's diagonal.
@@ -266,7 +266,19 @@ def lowest_modes(atoms, nev=1, constraints=None, free=None, tol=1e-8, block=None
 
     A pair counts as converged when |r| <= tol |theta|: the rule is RELATIVE, so an exact zero mode never converges.  A
     system that has them — nothing pinned in a periodic cell (three translations), a free cluster (six) — should have
-    atoms pinned, which removes them; otherwise `nconv < nev` raises RuntimeError unless `allow_unconverged=True`."""
+    atoms pinned, which removes them; otherwise `nconv < nev` raises RuntimeError unless `allow_unconverged=True`.
+
+    cell=True: the lowest curvatures over [free positions; cell], the cell in the coordinates of `CellCartesianPES`: the
+    log-deformation about the current cell, times `exp_cell_factor` (default N), at the entries `cell_mask` (3 x 3 bools,
+    default all) selects, with p V of `scalar_pressure` in the energy (device `EMT` in a fully periodic cell; block Davidson
+    on `DeviceHvpOperator.for_cell`, preconditioned with its diagonal).  V0 then has the mask's entries behind the free
+    coordinates, and the result one more key, `cell_modes` (nev, 3, 3): the cell part of every mode at the mask's
+    positions, zero elsewhere; `modes` and `cell_modes` TOGETHER are orthonormal.  Zero modes there: the three translations
+    unless an atom is pinned, and, with the full mask at a minimum (no stress), the three rotations of cell and atoms
+    together — use a triangular mask there, which leaves the cell no rotation."""
+    if cell:
+        return _lowest_cell_modes(atoms, nev, constraints, free, tol, block, maxiter, maxvec, V0, allow_unconverged, cell_mask,
+                                  exp_cell_factor, scalar_pressure)
     from .atoms import supports_hessian
     calc = getattr(atoms, 'calc', None)
     if not (supports_hessian(calc) and getattr(calc, 'library_form', False)):
@@ -292,3 +304,49 @@ def lowest_modes(atoms, nev=1, constraints=None, free=None, tol=1e-8, block=None
     modes[:, np.arange(n) if sel is None else sel] = out['V'].T
     return dict(lams=out['lams'], modes=modes.reshape(nev, len(atoms), 3), res=out['res'], niter=out['niter'],
                 nmatvec=out['nmatvec'], nconv=out['nconv'])
+
+
+def _lowest_cell_modes(atoms, nev, constraints, free, tol, block, maxiter, maxvec, V0, allow_unconverged, cell_mask,
+                       exp_cell_factor, scalar_pressure):
+    """`lowest_modes(cell=True)`."""
+    from .atoms import EMT
+    from .peswrapper import cell_param_maps
+    calc = getattr(atoms, 'calc', None)
+    if not (isinstance(calc, EMT) and calc.has_cell_hvp and getattr(calc, 'library_form', False)):
+        raise NotImplementedError(f'lowest_modes: {type(calc).__name__} has no Hessian-vector operator of positions and cell in '
+                                  'the library (device EMT has)')
+    if not np.all(atoms.pbc):
+        raise NotImplementedError('lowest_modes: cell=True needs a cell that is periodic in all three directions')
+    mask = np.ones((3, 3), dtype=bool) if cell_mask is None else np.asarray(cell_mask, dtype=bool).reshape((3, 3))
+    mc = int(mask.sum())
+    if mc == 0:
+        raise ValueError('lowest_modes: cell=True with an empty cell_mask')
+    n = 3 * len(atoms)
+    sel = _free_coordinates(atoms, constraints, free)
+    mx = n if sel is None else len(sel)
+    m = mx + mc
+    nev = int(nev)
+    if nev < 1 or nev > m:
+        raise ValueError(f'lowest_modes: nev = {nev} with {mx} free coordinates and {mc} of the cell')
+    if block is None:
+        block = min(16, max(nev, 4))
+    atoms.get_potential_energy()                                       # the evaluation the library calculator is made at
+    cell0 = np.array(atoms.get_cell(), dtype=np.float64)             # the log-deformation is taken about the current cell
+    factor = float(len(atoms)) if exp_cell_factor is None else float(exp_cell_factor)
+    J, G0, P = cell_param_maps(atoms, cell0, mask, factor, float(scalar_pressure))
+    dc = calc.device_calculator()
+    op = DeviceHvpOperator.for_cell(dc, np.asarray(atoms.positions, dtype=np.float64).ravel(),
+                                    cell0, J, 0.5 * (G0 + G0.T), P, free=sel)
+    out = dc.ctx.davidson_block(op, None, nev, block=min(int(block), m), tol=tol, maxiter=maxiter, maxvec=maxvec, V0=V0,
+                                diag=op.diagonal())
+    if out['nconv'] < nev and not allow_unconverged:
+        raise RuntimeError(f'lowest_modes: nconv = {out["nconv"]} of {nev} pairs converged in {out["niter"]} iterations '
+                           '(the stopping rule is relative: zero modes do not converge; pin an atom, and at a minimum take a '
+                           'triangular cell_mask)')
+    V = out['V']
+    modes = np.zeros((nev, n))
+    modes[:, np.arange(n) if sel is None else sel] = V[:mx].T
+    cell_modes = np.zeros((nev, 3, 3))
+    cell_modes[:, mask] = V[mx:].T
+    return dict(lams=out['lams'], modes=modes.reshape(nev, len(atoms), 3), cell_modes=cell_modes, res=out['res'],
+                niter=out['niter'], nmatvec=out['nmatvec'], nconv=out['nconv'])

@@ -448,7 +448,7 @@ class PES:
 
         Vs, AVs = Hproj.Vs, Hproj.AVs
         if self._hvp is not None:
-            self.nhvp += Hproj.calls                                 # products, not force calls
+            self._count_products(Hproj)
         elif not isinstance(Hproj, NumericalHessian):
             self.neval += Hproj.calls * (2 if threepoint else 1)     # force calls the library made itself
         # Ritz vectors of the collected full-space iterates (peswrapper.py:545-551)
@@ -458,6 +458,9 @@ class PES:
         _, X = eigh(Atilde)
         self.H.update(Vs @ X, AVs @ X)
         self.first_diag = False
+
+    def _count_products(self, Hproj):
+        self.nhvp += Hproj.calls                                     # products, not force calls
 
     def _library_fd_operator(self, Ufree, threepoint):
         """The finite-difference Hessian as a library object (`sella_fd_*`) when the calculator itself lives in the
@@ -1172,6 +1175,62 @@ def expm_frechet_3x3_contracted(U, G):
     return np.real(Vinv.T @ (f * (V.T @ G @ Vinv.T)) @ V.T)
 
 
+def _dEdC(atoms, stress, forces, scalar_pressure):
+    """(dE/dC (3 x 3, p V included) at fixed Cartesian positions, C) from the stress and the forces."""
+    sigma = voigt_to_matrix(stress) if np.size(stress) == 6 else np.asarray(stress, dtype=np.float64).reshape(3, 3)
+    sigma = sigma + scalar_pressure * np.eye(3)
+    C = np.array(atoms.get_cell(), dtype=np.float64)
+    volume = abs(np.linalg.det(C))
+    pos = np.asarray(atoms.positions, dtype=np.float64)
+    return np.linalg.solve(C.T, volume * sigma + pos.T @ forces), C
+
+
+def _masked_expm_derivatives(U, cell_mask):
+    """(D1 (m, 3, 3), D2 (m, m, 3, 3)): the first and second Frechet derivatives D expm(U)[E_m] and
+    D2 expm(U)[E_m, E_q] along the masked unit directions, from one 9 x 9 exponential per ordered pair: in
+    expm([[U, E1, 0], [0, U, E2], [0, 0, U]]) the (1,2) block is D expm(U)[E1] and the (1,3) block the E1-before-E2
+    half of the second derivative, which is that block plus the one with E1 and E2 swapped."""
+    dirs = []
+    for r, c in zip(*np.nonzero(cell_mask)):                         # row-major, the order of L[cell_mask]
+        E = np.zeros((3, 3))
+        E[r, c] = 1.0
+        dirs.append(E)
+    m = len(dirs)
+    D1, half = np.zeros((m, 3, 3)), np.zeros((m, m, 3, 3))
+    big = np.zeros((9, 9))
+    for k in range(3):
+        big[3 * k:3 * k + 3, 3 * k:3 * k + 3] = U
+    for i, E1 in enumerate(dirs):
+        for j, E2 in enumerate(dirs):
+            big[0:3, 3:6], big[3:6, 6:9] = E1, E2
+            X = expm(big)
+            half[i, j] = X[0:3, 6:9]
+            if j == 0:
+                D1[i] = X[0:3, 3:6]
+    return D1, half + half.transpose(1, 0, 2, 3)
+
+
+def cell_param_maps(atoms, orig_cell, cell_mask, exp_cell_factor, scalar_pressure, derivatives=_masked_expm_derivatives):
+    """(J (9, m), G0 (m, m), P (9, 9) or None) of `CellCartesianPES._cell_param_maps` at the geometry of `atoms`, for the
+    log-deformation about `orig_cell` times `exp_cell_factor` at the entries of `cell_mask` (3 x 3 bools), with p V of
+    `scalar_pressure`: one stress and force evaluation and m^2 9 x 9 exponentials."""
+    stress = np.asarray(atoms.get_stress(), dtype=np.float64)
+    forces = np.asarray(atoms.get_forces(), dtype=np.float64).reshape((-1, 3))
+    dEdC, C = _dEdC(atoms, stress, forces, scalar_pressure)
+    P = None
+    if scalar_pressure != 0.0:
+        Ci = np.linalg.inv(C)
+        # d2 det C / dC_ab dC_cd = det C (C^-1_ba C^-1_dc - C^-1_da C^-1_bc)
+        d2 = np.einsum('ba,dc->abcd', Ci, Ci) - np.einsum('da,bc->abcd', Ci, Ci)
+        P = scalar_pressure * abs(np.linalg.det(C)) * d2.reshape(9, 9)
+    U = logm_3x3(C @ np.linalg.inv(orig_cell))
+    D1, D2 = derivatives(U, cell_mask)
+    J = (D1 @ orig_cell).reshape(len(D1), 9).T / exp_cell_factor    # (9, m)
+    dEdF = dEdC @ orig_cell.T
+    G0 = np.einsum('ab,mqab->mq', dEdF, D2) / exp_cell_factor ** 2
+    return J, G0, P
+
+
 class CellCartesianPES(PES):
     """`PES` with the unit cell as extra coordinates (Cartesian positions + masked log-deformation of the cell).
 
@@ -1207,6 +1266,7 @@ class CellCartesianPES(PES):
         nc = self.ncart
         self.dim = nc + self.n_cell_dof
         self._cell_hvp_source, self._cell_maps_cache = cell_hvp, _LRU2()
+        self._cell_hvp_from_calc = cell_hessian_vector_product is True
         if cell_hvp is not None:
             self._hvp = self._cell_hvp                           # what `PES.diag` takes its products from
         if H0 is not None:
@@ -1299,12 +1359,7 @@ class CellCartesianPES(PES):
 
     def _dEdC(self, stress, forces):
         """(dE/dC (3 x 3, p V included) at fixed Cartesian positions, C) from the stress and the forces."""
-        sigma = voigt_to_matrix(stress) if np.size(stress) == 6 else np.asarray(stress, dtype=np.float64).reshape(3, 3)
-        sigma = sigma + self.scalar_pressure * np.eye(3)
-        C = self._cell()
-        volume = abs(np.linalg.det(C))
-        pos = np.asarray(self.atoms.positions, dtype=np.float64)
-        return np.linalg.solve(C.T, volume * sigma + pos.T @ forces), C
+        return _dEdC(self.atoms, stress, forces, self.scalar_pressure)
 
     def _cell_gradient(self, stress, forces):
         dEdC, C = self._dEdC(stress, forces)
@@ -1315,28 +1370,8 @@ class CellCartesianPES(PES):
 
     # ---- exact Hessians: hessian_function in the coordinates [x; C.ravel()] -------------------------------------
     def _expm_derivatives(self, U):
-        """(D1 (m, 3, 3), D2 (m, m, 3, 3)): the first and second Frechet derivatives D expm(U)[E_m] and
-        D2 expm(U)[E_m, E_q] along the masked unit directions, from one 9 x 9 exponential per ordered pair: in
-        expm([[U, E1, 0], [0, U, E2], [0, 0, U]]) the (1,2) block is D expm(U)[E1] and the (1,3) block the E1-before-E2
-        half of the second derivative, which is that block plus the one with E1 and E2 swapped."""
-        dirs = []
-        for r, c in zip(*np.nonzero(self.cell_mask)):                    # row-major, the order of L[cell_mask]
-            E = np.zeros((3, 3))
-            E[r, c] = 1.0
-            dirs.append(E)
-        m = len(dirs)
-        D1, half = np.zeros((m, 3, 3)), np.zeros((m, m, 3, 3))
-        big = np.zeros((9, 9))
-        for k in range(3):
-            big[3 * k:3 * k + 3, 3 * k:3 * k + 3] = U
-        for i, E1 in enumerate(dirs):
-            for j, E2 in enumerate(dirs):
-                big[0:3, 3:6], big[3:6, 6:9] = E1, E2
-                X = expm(big)
-                half[i, j] = X[0:3, 6:9]
-                if j == 0:
-                    D1[i] = X[0:3, 3:6]
-        return D1, half + half.transpose(1, 0, 2, 3)
+        """`_masked_expm_derivatives` along the directions of this PES's mask."""
+        return _masked_expm_derivatives(U, self.cell_mask)
 
     def _cell_param_maps(self):
         """(J (9, m), G0 (m, m), P (9, 9) or None) of the current geometry, what carries second derivatives from
@@ -1349,22 +1384,8 @@ class CellCartesianPES(PES):
         hit = self._cell_maps_cache.get(key)
         if hit is not None:
             return hit
-        fac = self.exp_cell_factor
-        stress = np.asarray(self.atoms.get_stress(), dtype=np.float64)
-        forces = np.asarray(self.atoms.get_forces(), dtype=np.float64).reshape((-1, 3))
-        dEdC, C = self._dEdC(stress, forces)
-        P = None
-        if self.scalar_pressure != 0.0:
-            Ci = np.linalg.inv(C)
-            # d2 det C / dC_ab dC_cd = det C (C^-1_ba C^-1_dc - C^-1_da C^-1_bc)
-            d2 = np.einsum('ba,dc->abcd', Ci, Ci) - np.einsum('da,bc->abcd', Ci, Ci)
-            P = self.scalar_pressure * abs(np.linalg.det(C)) * d2.reshape(9, 9)
-        U = logm_3x3(C @ np.linalg.inv(self.orig_cell))
-        D1, D2 = self._expm_derivatives(U)
-        J = (D1 @ self.orig_cell).reshape(len(D1), 9).T / fac             # (9, m)
-        dEdF = dEdC @ self.orig_cell.T
-        G0 = np.einsum('ab,mqab->mq', dEdF, D2) / fac ** 2
-        out = (J, G0, P)
+        out = cell_param_maps(self.atoms, self.orig_cell, self.cell_mask, self.exp_cell_factor, self.scalar_pressure,
+                              derivatives=lambda U, _mask: self._expm_derivatives(U))
         self._cell_maps_cache.put(key, out)
         return out
 
@@ -1414,6 +1435,43 @@ class CellCartesianPES(PES):
         if P is not None:
             yC = yC + W @ P.T
         return np.hstack([Y[:, :nc], yC @ J + Vp @ (0.5 * (G0 + G0.T)).T])
+
+    def _library_hvp_operator(self, Ufree):
+        """The Hessian of positions and cell as a library object (`sella_hvp_create_cell`, `DeviceHvpOperator.for_cell`)
+        when the products are the calculator's own (`cell_hessian_vector_product=True`) and the calculator lives in the
+        library as EMT: the state of this geometry, with J, G and P of `_cell_param_maps`, is built once and the products of
+        the Davidson run never leave the device.  Needs what `PES._library_fd_operator` needs: nobody listening per
+        evaluation, no curved constraints, `use_library_calculator` not False, and a basis that selects coordinates (its
+        cell part is always the identity).  Else None: the host operator over `_cell_hvp`."""
+        from .atoms import EMT
+        calc = getattr(self.atoms, 'calc', None)
+        if not self._cell_hvp_from_calc or not isinstance(calc, EMT) or self.traj is not None:
+            return None
+        maker = calc.device_calculator
+        if self._has_curved_constraints() or getattr(self, 'use_library_calculator', True) is False:
+            return None
+        # constraints that each pin one coordinate make the basis a selection of position coordinates with the identity of
+        # the cell behind it (`_split_cons_subspace`); none make it the identity; any other basis mixes coordinates
+        free = None
+        if PES.get_drdx(self).shape[0] > 0:
+            pinned = self._pinned()
+            if pinned is None:
+                return None
+            free = np.setdiff1d(np.arange(self.ncart), pinned[0])
+        dc = maker()
+        if dc is None:
+            return None
+        from .device import DeviceHvpOperator
+        J, G0, P = self._cell_param_maps()
+        return DeviceHvpOperator.for_cell(dc, self.apos.ravel(), self._cell(), J, 0.5 * (G0 + G0.T), P, free=free)
+
+    def _count_products(self, Hproj):
+        """`PES._count_products`; the calculator counts every product of the device route as a batch of one (`ncellhvps`),
+        as it would through the host."""
+        from .device import DeviceHvpOperator
+        PES._count_products(self, Hproj)
+        if isinstance(Hproj, DeviceHvpOperator):
+            self.atoms.calc.ncellhvps += Hproj.calls
 
     def _convert_cell_hessian(self, H, consume=False):
         """The Hessian in the PES's coordinates [x; p] of what a `hessian_function` returns in a cell run: the

@@ -16,8 +16,17 @@ around calls that end in a stream synchronisation, all of them alternated in one
                   expm -> set_cell, a fresh image set-up, one force-and-virial pass per product), the route `diag` took
                   in a cell run before
   dense       (d) `calc.get_device_cell_hessian` of a geometry not seen before (the dense (3N + 9)-square Hessian)
-Each sample is the time of the whole batch of K products (or the one dense Hessian); median, minimum, maximum and the
-quartiles over the repetitions are reported.  The products of (a) are checked against the dense Hessian of (d)."""
+  op_1        (e) K single products through the resident operator of positions and cell (`DeviceHvpOperator.for_cell`,
+                  `sella_hvp_matvec` with host vectors), the operator made once outside the clock
+  op_create       making that operator: density pass, F2, the image indices, J, G and P uploaded — once per geometry
+  op_block    (f) one block product of K rows on it (`sella_hvp_apply_block`)
+  diag_dev    (g) one whole `CellCartesianPES.diag(maxiter=K)` (at most K products) with
+                  the first atom pinned, on the device route ...
+  diag_host       ... and on the host route (`use_library_calculator = False`); two PES objects that see the same sequence
+                  of calls, so repetition r of the one answers repetition r of the other
+Each sample is the time of the whole batch of K products (or the one dense Hessian, operator or diagonalisation); median,
+minimum, maximum and the quartiles over the repetitions are reported.  The products of (a) are checked against the dense
+Hessian of (d), those of (f) against the same Hessian carried into the coordinates of the PES."""
 import argparse
 import json
 import os
@@ -28,7 +37,8 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sella_amd.atoms import EMT, Atoms  # noqa: E402
-from sella_amd.device import get_context  # noqa: E402
+from sella_amd.device import DeviceHvpOperator, get_context  # noqa: E402
+from sella_amd.internal import Constraints  # noqa: E402
 from sella_amd.linalg import NumericalHessian  # noqa: E402
 from sella_amd.peswrapper import CellCartesianPES  # noqa: E402
 
@@ -73,8 +83,30 @@ def measure(rep, k, reps, warmup):
         for v in Vp:
             pes._hvp(v[None, :])
 
+    J, G0, P = pes._cell_param_maps()
+    dc = calc.device_calculator()
+    op_args = (dc, at.positions.ravel().copy(), np.array(at.cell, dtype=float), J, 0.5 * (G0 + G0.T), P)
+    op = DeviceHvpOperator.for_cell(*op_args)
+    out1 = np.empty(pes.dim)
+
+    def op_single():
+        for v in Vp:
+            out1[:] = op.apply(v)
+
+    def pinned_pes(library):
+        atoms = bulk(rep)
+        cons = Constraints(atoms)
+        cons.fix_translation(0)
+        p = CellCartesianPES(atoms, cell_hessian_vector_product=True, constraints=cons)
+        p.use_library_calculator = library
+        p.get_g()
+        return p
+    pes_dev, pes_host = pinned_pes(True), pinned_pes(False)
+
     calls = dict(cell_hvp=lambda: calc.cell_hessian_vector_product(at, V), cell_hvp_1=one_at_a_time,
-                 hvp=lambda: calc.hessian_vector_product(at, V[:, :n]), fd=fd, dense=dense)
+                 hvp=lambda: calc.hessian_vector_product(at, V[:, :n]), fd=fd, dense=dense,
+                 op_1=op_single, op_create=lambda: DeviceHvpOperator.for_cell(*op_args), op_block=lambda: op.apply_block(Vp),
+                 diag_dev=lambda: pes_dev.diag(maxiter=k), diag_host=lambda: pes_host.diag(maxiter=k))
     for fn in calls.values():
         for _ in range(warmup):
             fn()
@@ -95,7 +127,13 @@ def measure(rep, k, reps, warmup):
     HV = calc.cell_hessian_vector_product(at, V)
     out['max_abs_err_vs_dense'] = float(np.abs(HV - V @ H).max())
     out['err_bound'] = float(2 * (n + 9) * np.finfo(float).eps * np.abs(H).sum(axis=1).max() * np.abs(V).max())
+    Hp = pes._convert_cell_hessian(H)
+    out['op_block_max_abs_err_vs_dense'] = float(np.abs(op.apply_block(Vp) - Vp @ Hp).max())
+    out['op_block_err_bound'] = float(2 * (pes.dim + 18) * np.finfo(float).eps * np.abs(Hp).sum(axis=1).max() * np.abs(Vp).max())
+    out['diag_products'] = dict(dev=pes_dev.nhvp, host=pes_host.nhvp, calls=reps + warmup)
     med = {name: out[name]['median_ms'] for name in calls}
+    out['cell_hvp_1_over_op_1'] = med['cell_hvp_1'] / med['op_1']
+    out['diag_host_over_diag_dev'] = med['diag_host'] / med['diag_dev']
     out['fd_over_cell_hvp'] = med['fd'] / med['cell_hvp']
     out['fd_over_cell_hvp_1'] = med['fd'] / med['cell_hvp_1']
     out['cell_hvp_over_hvp'] = med['cell_hvp'] / med['hvp']
@@ -104,14 +142,15 @@ def measure(rep, k, reps, warmup):
 
 
 def table(results):
-    names = ('cell_hvp', 'cell_hvp_1', 'hvp', 'fd', 'dense')
-    lines = ['| N | k | ' + ' | '.join(f'{name} ms (min .. max; quartiles)' for name in names) + ' | fd / cell_hvp | cell_hvp / hvp | dense / cell_hvp |',
-             '|---|---|' + '---|' * (len(names) + 3)]
+    names = ('cell_hvp', 'cell_hvp_1', 'hvp', 'fd', 'dense', 'op_1', 'op_create', 'op_block', 'diag_dev', 'diag_host')
+    lines = ['| N | k | ' + ' | '.join(f'{name} ms (min .. max; quartiles)' for name in names) + ' | fd / cell_hvp | cell_hvp / hvp | dense / cell_hvp | cell_hvp_1 / op_1 | diag_host / diag_dev |',
+             '|---|---|' + '---|' * (len(names) + 5)]
     for r in results:
         cells = [f"{r[m]['median_ms']:.3f} ({r[m]['min_ms']:.3f} .. {r[m]['max_ms']:.3f}; {r[m]['q1_ms']:.3f}, {r[m]['q3_ms']:.3f})"
                  for m in names]
         lines.append(f"| {r['natoms']} | {r['k']} | " + ' | '.join(cells)
-                     + f" | {r['fd_over_cell_hvp']:.1f} | {r['cell_hvp_over_hvp']:.2f} | {r['dense_over_cell_hvp']:.2f} |")
+                     + f" | {r['fd_over_cell_hvp']:.1f} | {r['cell_hvp_over_hvp']:.2f} | {r['dense_over_cell_hvp']:.2f}"
+                     + f" | {r['cell_hvp_1_over_op_1']:.1f} | {r['diag_host_over_diag_dev']:.2f} |")
     return '\n'.join(lines)
 
 
@@ -134,6 +173,14 @@ def main():
     slower = [r['natoms'] for r in results if not r['cell_hvp']['median_ms'] < r['fd']['median_ms']]
     if slower:
         sys.exit(f'the exact product is not faster than the finite-difference route at N = {slower}')
+    # the resident operator: its single products against the one-at-a-time route (the spreads must not touch), and the whole
+    # diagonalisation against the host route
+    slower = [r['natoms'] for r in results if not r['op_1']['max_ms'] < r['cell_hvp_1']['min_ms']]
+    if slower:
+        sys.exit(f'single products on the resident operator are not clear of the one-at-a-time route at N = {slower}')
+    slower = [r['natoms'] for r in results if not r['diag_dev']['median_ms'] < r['diag_host']['median_ms']]
+    if slower:
+        sys.exit(f'diag() on the device route is not faster than on the host route at N = {slower}')
 
 
 if __name__ == '__main__':
