@@ -6,10 +6,14 @@
 //   1. Blocked Householder tridiagonalisation  Q^T A Q = T  (panels of nb columns, LAPACK
 //      dlatrd's algebra).  The full symmetric trailing matrix is kept, so the matrix-vector
 //      product of each column is the row-panel matvec of the Davidson loop (coalesced 16-byte
-//      streams, wave64 reductions).  Per column exactly TWO launches: `trd_row_kernel`
+//      streams, wave64 reductions).  Per column two launches: `trd_row_kernel`
 //      (finish the previous w, form the updated row, partial norms / panel dots) and
 //      `trd_gemv_kernel` (reflector scalars from the partials, v staged on the fly, A22 v);
-//      the rank-2nb trailing update is two GEMMs per panel.
+//      per panel one more row launch that only finishes the last w, and the rank-2nb trailing
+//      update as one streaming MFMA pass (update.hip).  Where that pass runs on the full block
+//      it also leaves row 0 of the updated block, its diagonal entry and the partials of its
+//      sum of squares for the next panel, whose first column then has no row launch:
+//      2 nb launches per panel of the chain instead of 2 nb + 1.
 //   2. Divide and conquer on T (Cuppen, with Gu/Eisenstat's stable eigenvectors): leaves by
 //      implicit QL (one wavefront per leaf), merges = deflation (host, O(N log N)) + secular
 //      equation (one wavefront per root) + one GEMM per merge; two host synchronisations per
@@ -30,7 +34,8 @@ namespace sella {
 namespace {
 
 constexpr int TRD_NBMAX = 64;              // max panel width
-constexpr int TRD_PA = 1;                  // doubles per block in the K1 partial buffer (sum u^2)
+constexpr int TRD_PA = 1;                  // doubles per partial in the K1 partial buffer (sum u^2)
+constexpr int TRD_PAW = 4;                 // partials per workgroup of trd_row_kernel: one per wavefront
 constexpr int WY_NB = 32;                  // reflectors per compact-WY block
 
 __device__ __forceinline__ double wave_sum_e(double v) { return wave_sum64(v); }
@@ -66,10 +71,12 @@ struct TrdRowArgs {
 // K1.  Thread owns absolute column c = j + blockIdx.x*256 + tid.
 //   (1) i > 0: finish w_{i-1} = tau (wraw - V c1 - W c2) + alpha2 v   (dlatrd), store in Wp
 //   (2) u[c] = A[j][c] - sum_{p<i} (V_p[c] W_p[j] + W_p[c] V_p[j])    (pending rank-2i update)
-//   (3) per-block partial of sum u^2 (c >= j+2)
+//   (3) per-WAVEFRONT partial of sum u^2 (c >= j+2): TRD_PAW per workgroup, added up by the matvec
 // The kernel sits on the critical path of the factorisation (n dependent launches), so it is laid
 // out for latency: every global load is issued before the first barrier, the panel is read once for
-// both sums, and the only block-wide exchanges are the reduction of the v.wraw partials and of u^2.
+// both sums, and the only block-wide exchange is the reduction of the v.wraw partials (i > 0).
+// At a panel seam behind the streaming trailing update the launch for i = 0 does not run at all: the
+// update has written u, dvec[j] and the partials (rank2k_seam_row, update.hip).
 // IPC >= 0: number of finished panel columns (i - 1) as a compile-time constant, so the panel loop
 // is fully unrolled with all its loads in flight together; IPC < 0: generic loop (wide panels).
 template <int IPC>
@@ -185,9 +192,9 @@ __global__ __launch_bounds__(256) void trd_row_kernel(TrdRowArgs a) {
         a.u_cur[c] = u;
         if (c == j) a.dvec[j] = u;
     }
-    double ss = (valid && c >= j + 2) ? u * u : 0.0;
-    ss = block_sum_256(ss, red);
-    if (tid == 0) a.partA_cur[(size_t)blockIdx.x * TRD_PA] = ss;
+    // one partial per WAVEFRONT (the matvec adds up however many there are): no block-wide exchange behind the store of u
+    const double ss = wave_sum_e((valid && c >= j + 2) ? u * u : 0.0);
+    if ((tid & 63) == 0) a.partA_cur[(size_t)(TRD_PAW * blockIdx.x + (tid >> 6)) * TRD_PA] = ss;
 }
 
 __device__ __forceinline__ double2 ldg2(const double* p) { return *reinterpret_cast<const double2*>(p); }
@@ -240,11 +247,12 @@ __global__ __launch_bounds__(256) void trd_gemv_kernel(TrdGemvArgs a) {
         arow[r] = reinterpret_cast<const double2*>(base);
         lead[r] = base[a.shift];
     }
-    // K1 partials of sum u^2 (one per lane, reduced after the stream) and the entries of u this
-    // workgroup's epilogue needs: issued now, consumed at the end
+    // partials of sum u^2 (one per wavefront of the row kernel, or one per tile column of the trailing update at a panel
+    // seam; one per lane, reduced after the stream) and the entries of u this workgroup's epilogue needs: issued now,
+    // consumed at the end
     double ssl0 = a.partA[(size_t)(lane < a.nblkA ? lane : a.nblkA - 1) * TRD_PA];     // consumed after the stream
     double ssl = 0.0;
-    for (int b = lane + 64; b < a.nblkA; b += 64) ssl += a.partA[(size_t)b * TRD_PA];  // (n > 16384 only)
+    for (int b = lane + 64; b < a.nblkA; b += 64) ssl += a.partA[(size_t)b * TRD_PA];  // (n > 4096 only)
     const double alpha = a.ubuf[a.o];
     double urow[2];
 #pragma unroll
@@ -2444,7 +2452,7 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
     // the entries in front of it — left over from the previous panel — only ever meet the zeros of the masked row u',
     // so they must be finite, nothing more: the shared scratch may hold anything before the first panel.
     HIPCHK(s_memset0(c, Vp, (size_t)2 * nb * ld * sizeof(double)));
-    const int maxblkA = (n + 255) / 256 + 1, maxblkB = (n + 16 + 2 * TRD_NBMAX + 1) / 2 + 1;
+    const int maxblkA = TRD_PAW * ((n + 255) / 256) + 1, maxblkB = (n + 16 + 2 * TRD_NBMAX + 1) / 2 + 1;
     SCHK(scratch_get(c, SCR_MISC1, ((size_t)2 * maxblkA * TRD_PA + 2 * (size_t)maxblkB + 4 * TRD_NBMAX + 128) * sizeof(double), &part));
     double* partA[2] = {part, part + (size_t)maxblkA * TRD_PA};
     double* partB = part + 2 * (size_t)maxblkA * TRD_PA;
@@ -2471,10 +2479,17 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
     const int tail_lds = (int)std::min<long>(c->opt.eigh_tail_lds, TRD_TAIL);
     bool lower_stale = false;                          // the trailing update has been writing the upper triangle only
     const bool can_tri = c->opt.rank2k_stream;
+    // which stage takes the panel that starts at column jn (with the full block up to date in front of it)
+    auto to_lds_tail = [&](int jn) { return tail_lds > 0 && n - jn <= tail_lds; };
+    auto to_upd_chain = [&](int jn) {
+        return upd_max > 0 && n - jn - 1 <= upd_max && !to_lds_tail(jn) && !(symv_min > 0 && n - jn - 1 >= symv_min);
+    };
+    // the trailing update of the previous panel has left row j0 of the updated block, its diagonal entry and the partials
+    // of its sum of squares where the first row launch of this panel would have put them: that launch is skipped
+    bool seam_done = false;
     for (int j0 = 0; j0 < nrefl; j0 += nb) {
         const int kb = std::min(nb, nrefl - j0);
-        if (upd_max > 0 && !lower_stale && n - j0 - 1 <= upd_max && !(tail_lds > 0 && n - j0 <= tail_lds) &&
-            !(symv_min > 0 && n - j0 - 1 >= symv_min)) {
+        if (!lower_stale && to_upd_chain(j0)) {
             // ---- small trailing block: one launch per column from here to the LDS tail (or to the end)
             const int jend = tail_lds > 0 ? std::min(nrefl, n - tail_lds) : nrefl;
             int fc = 0, nblk_last = 0;
@@ -2536,7 +2551,7 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
             j0 = jend - nb;                                 // (the loop adds nb: the next pass starts at jend)
             continue;
         }
-        if (tail_lds > 0 && n - j0 <= tail_lds) {
+        if (to_lds_tail(j0)) {
             // the rest of the factorisation inside one workgroup (the trailing block is up to date at a panel boundary)
             prof_begin(c, PROF_OTHER, 8.0 * (n - j0) * (double)(n - j0), 0.0);
             SELLA_LAUNCH(c, trd_tail_lds_kernel, dim3(1), dim3(1024), 0, W.A, ld, n, j0, dvec, evec, taus);
@@ -2560,8 +2575,9 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
             ra.colscal = colscal;
             ra.cdots = cdots;
             ra.dvec = dvec;
-            const int nblkA = (n - j + 255) / 256;
-            const dim3 gA(nblkA), bA(256);
+            const bool seam_row = i == 0 && seam_done;          // row j and its partials came with the trailing update
+            const dim3 gA((n - j + 255) / 256), bA(256);
+            const int nblkA = seam_row ? nblkA_prev : TRD_PAW * (int)gA.x;
             // Profiling samples every 4th column.  The event pair is attached to the dispatch packet, whose
             // start stamp is taken when the packet is picked up — behind a backlog of earlier launches that
             // would include queueing time.  So the queue is drained first and then BOTH kernels of the column
@@ -2570,22 +2586,25 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
             const bool prof_all = c->prof;
             if (prof_all && (j & 3)) c->prof = false;
             if (c->prof) SCHK(stream_wait(c));
-            prof_begin(c, PROF_OTHER, 8.0 * (2.0 * i + 3.0) * (n - j), 0.0);
-            switch (i - 1) {
+            if (!seam_row) {
+                prof_begin(c, PROF_OTHER, 8.0 * (2.0 * i + 3.0) * (n - j), 0.0);
+                switch (i - 1) {
 #define SELLA_TRD_ROW_CASE(IP) case IP: SELLA_LAUNCH(c, HIP_KERNEL_NAME(trd_row_kernel<IP>), gA, bA, 0, ra); break;
-                case -1:
-                SELLA_TRD_ROW_CASE(0) SELLA_TRD_ROW_CASE(1) SELLA_TRD_ROW_CASE(2) SELLA_TRD_ROW_CASE(3)
-                SELLA_TRD_ROW_CASE(4) SELLA_TRD_ROW_CASE(5) SELLA_TRD_ROW_CASE(6) SELLA_TRD_ROW_CASE(7)
-                SELLA_TRD_ROW_CASE(8) SELLA_TRD_ROW_CASE(9) SELLA_TRD_ROW_CASE(10) SELLA_TRD_ROW_CASE(11)
-                SELLA_TRD_ROW_CASE(12) SELLA_TRD_ROW_CASE(13) SELLA_TRD_ROW_CASE(14) SELLA_TRD_ROW_CASE(15)
-                SELLA_TRD_ROW_CASE(16) SELLA_TRD_ROW_CASE(17) SELLA_TRD_ROW_CASE(18) SELLA_TRD_ROW_CASE(19)
-                SELLA_TRD_ROW_CASE(20) SELLA_TRD_ROW_CASE(21) SELLA_TRD_ROW_CASE(22) SELLA_TRD_ROW_CASE(23)
-                SELLA_TRD_ROW_CASE(24) SELLA_TRD_ROW_CASE(25) SELLA_TRD_ROW_CASE(26) SELLA_TRD_ROW_CASE(27)
-                SELLA_TRD_ROW_CASE(28) SELLA_TRD_ROW_CASE(29) SELLA_TRD_ROW_CASE(30) SELLA_TRD_ROW_CASE(31)
+                    case -1:
+                    SELLA_TRD_ROW_CASE(0) SELLA_TRD_ROW_CASE(1) SELLA_TRD_ROW_CASE(2) SELLA_TRD_ROW_CASE(3)
+                    SELLA_TRD_ROW_CASE(4) SELLA_TRD_ROW_CASE(5) SELLA_TRD_ROW_CASE(6) SELLA_TRD_ROW_CASE(7)
+                    SELLA_TRD_ROW_CASE(8) SELLA_TRD_ROW_CASE(9) SELLA_TRD_ROW_CASE(10) SELLA_TRD_ROW_CASE(11)
+                    SELLA_TRD_ROW_CASE(12) SELLA_TRD_ROW_CASE(13) SELLA_TRD_ROW_CASE(14) SELLA_TRD_ROW_CASE(15)
+                    SELLA_TRD_ROW_CASE(16) SELLA_TRD_ROW_CASE(17) SELLA_TRD_ROW_CASE(18) SELLA_TRD_ROW_CASE(19)
+                    SELLA_TRD_ROW_CASE(20) SELLA_TRD_ROW_CASE(21) SELLA_TRD_ROW_CASE(22) SELLA_TRD_ROW_CASE(23)
+                    SELLA_TRD_ROW_CASE(24) SELLA_TRD_ROW_CASE(25) SELLA_TRD_ROW_CASE(26) SELLA_TRD_ROW_CASE(27)
+                    SELLA_TRD_ROW_CASE(28) SELLA_TRD_ROW_CASE(29) SELLA_TRD_ROW_CASE(30) SELLA_TRD_ROW_CASE(31)
 #undef SELLA_TRD_ROW_CASE
-                default: SELLA_LAUNCH(c, HIP_KERNEL_NAME(trd_row_kernel<-1>), gA, bA, 0, ra);
+                    default: SELLA_LAUNCH(c, HIP_KERNEL_NAME(trd_row_kernel<-1>), gA, bA, 0, ra);
+                }
+                prof_end(c);
             }
-            prof_end(c);
+            seam_done = false;
             if (!do_row) { c->prof = prof_all; break; }
             const int o = j + 1, m = n - o, oc = o & ~1;
             TrdGemvArgs ga;
@@ -2663,6 +2682,12 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
                     SCHK(launch_mirror_upper(c, At, mt, ld));
                     lower_stale = false;
                 }
+            } else if (c->opt.rank2k_stream && aligned && r0 < nrefl && !to_upd_chain(r0) && !to_lds_tail(r0)) {
+                // full block through the streaming kernels and another panel of the blocked chain behind it: the update
+                // carries the seam (row r0 of the updated block -> u, d[r0], partials of sum u^2)
+                const Rank2kSeam seam = {ub[cur] + r0, dvec + r0, partA[cur]};
+                SCHK(launch_rank2k_stream_seam(c, At, mt, ld, Vp + r0, Wp + r0, ld, kb, -1.0, seam, &nblkA_prev));
+                seam_done = true;
             } else if (c->opt.rank2k_stream) SCHK(launch_rank2k_stream(c, At, mt, ld, Vp + r0, Wp + r0, ld, kb, -1.0));
             else SCHK(launch_sym_rank2k(c, At, mt, ld, Vp + r0, Wp + r0, ld, kb, -1.0));
         }

@@ -357,6 +357,13 @@ int launch_sym_rank2k(sella_ctx* c, double* B, int n, int ld, const double* Up, 
 // triangles agree to roundoff, not bitwise): the trailing update of the tridiagonalisation
 int launch_rank2k_stream(sella_ctx* c, double* C, int m, int ld, const double* Up, const double* Zp, int ldp, int kk,
                          double alpha, bool upper_only = false);
+// The same update of the full block, carrying the panel seam of the blocked tridiagonalisation: the workgroups that own
+// row 0 of the updated block also leave it in u[0 .. m), its leading entry in d[0] and one partial of its sum of squares over
+// the columns >= 2 per tile column in partA[0 .. *npart) — what the first row launch of the next panel would have computed.
+// Needs the streaming kernels (ld even, C 16-byte aligned: SELLA_E_INVALID otherwise).
+struct Rank2kSeam { double* u; double* d; double* partA; };
+int launch_rank2k_stream_seam(sella_ctx* c, double* C, int m, int ld, const double* Up, const double* Zp, int ldp, int kk,
+                              double alpha, const Rank2kSeam& seam, int* npart);
 int launch_mirror_upper(sella_ctx* c, double* C, int m, int ld);      // lower triangle <- transpose of the upper one
 // eigh.hip: eigendecomposition (w host ascending, Vt rows / V columns, both updated in place) of
 // B + sum_a (U_a Z_a^T + Z_a U_a^T) from that of B; *nrank1 = rank-one modifications applied

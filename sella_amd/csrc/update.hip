@@ -104,10 +104,37 @@ __global__ __launch_bounds__(256) void sym_rank2k_kernel(double* __restrict__ B,
 typedef double upd_f64x4 __attribute__((ext_vector_type(4)));
 constexpr int RS_TR = 32, RS_TC = 128;
 
-__global__ __launch_bounds__(256) void rank2k_stream_kernel(double* __restrict__ C, int m, int ld,
-                                                            const double* __restrict__ Up,
-                                                            const double* __restrict__ Zp, int ldp, int kk,
-                                                            double alpha) {
+// One argument block for both kernels.  seam_u != nullptr: the panel seam of the blocked tridiagonalisation rides along
+// (launch_rank2k_stream_seam, internal.h).
+struct Rank2kStreamArgs {
+    double* C; int m, ld;
+    const double* Up; const double* Zp; int ldp, kk;
+    double alpha;
+    int upper_only;
+    double* seam_u; double* seam_d; double* seam_partA;
+};
+
+// Seam epilogue, written once for both kernels (explicit fma: the same bits from either).  Called by all 64 lanes of the
+// wavefront that holds row 0 of the block in the row-major pass, lane -> columns cidx, cidx + 1 (cidx even) with the updated
+// pair (ux, uy): the row goes to seam_u, its entry in column 0 to seam_d, and the wavefront's sum of squares over the
+// columns >= 2 — one partial per tile column — to seam_partA.
+__device__ __forceinline__ void rank2k_seam_row(const Rank2kStreamArgs& a, int cidx, double ux, double uy) {
+    const bool ok0 = cidx < a.m, ok1 = cidx + 1 < a.m;
+    if (ok0) a.seam_u[cidx] = ux;
+    if (ok1) a.seam_u[cidx + 1] = uy;
+    if (cidx == 0) a.seam_d[0] = ux;
+    double s = (ok0 && cidx >= 2) ? ux * ux : 0.0;
+    s = (ok1 && cidx >= 2) ? fma(uy, uy, s) : s;
+    s = wave_sum64(s);
+    if ((threadIdx.x & 63) == 0) a.seam_partA[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void rank2k_stream_kernel(Rank2kStreamArgs a) {
+    double* __restrict__ C = a.C;
+    const double* __restrict__ Up = a.Up;
+    const double* __restrict__ Zp = a.Zp;
+    const int m = a.m, ld = a.ld, ldp = a.ldp, kk = a.kk;
+    const double alpha = a.alpha;
     __shared__ double dl[RS_TR][RS_TC + 2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lq = lane >> 4;
@@ -126,12 +153,12 @@ __global__ __launch_bounds__(256) void rank2k_stream_kernel(double* __restrict__
         // X[r][k] = (k < kk ? U[k][r] : Z[k - kk][r]);  Y[c][k] = (k < kk ? Z[k][c] : U[k - kk][c])
         const double* xrow = (kc < kk) ? Up + (size_t)kc * ldp : Zp + (size_t)(kc - kk) * ldp;
         const double* yrow = (kc < kk) ? Zp + (size_t)kc * ldp : Up + (size_t)(kc - kk) * ldp;
-        const double a = ok ? xrow[rr] : 0.0;
+        const double xa = ok ? xrow[rr] : 0.0;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int cc = wc + 16 * t + li;
-            const double b = (ok && cc < m) ? yrow[cc] : 0.0;
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[t], 0, 0, 0);
+            const double yb = (ok && cc < m) ? yrow[cc] : 0.0;
+            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, yb, acc[t], 0, 0, 0);
         }
     }
     // fragments -> LDS (C/D layout of the f64 MFMA: row = (lane >> 4) + 4 reg, col = lane & 15)
@@ -145,18 +172,21 @@ __global__ __launch_bounds__(256) void rank2k_stream_kernel(double* __restrict__
 #pragma unroll
     for (int s8 = 0; s8 < RS_TR; s8 += 4) {
         const int r = r0 + s8 + pr, cidx = c0 + 2 * pc;
+        double2 v = make_double2(0.0, 0.0);
         if (r < m && cidx < m) {
             double* p = C + (size_t)r * ld + cidx;
             const double d0 = dl[s8 + pr][2 * pc], d1 = dl[s8 + pr][2 * pc + 1];
             if (cidx + 1 < m) {
-                double2 v = *reinterpret_cast<double2*>(p);
+                v = *reinterpret_cast<double2*>(p);
                 v.x += alpha * d0;
                 v.y += alpha * d1;
                 *reinterpret_cast<double2*>(p) = v;
             } else {
-                p[0] += alpha * d0;
+                v.x = p[0] + alpha * d0;
+                p[0] = v.x;
             }
         }
+        if (s8 == 0 && a.seam_u && r == 0) rank2k_seam_row(a, cidx, v.x, v.y);     // (r == 0: uniform over the wavefront)
     }
 }
 
@@ -172,10 +202,12 @@ __global__ __launch_bounds__(256) void rank2k_stream_kernel(double* __restrict__
 // it transposed (half the MFMA work: 16.2-16.8 us, but the two triangles then differ from this kernel's by rounding,
 // which moves the Davidson trajectories for 0.05 ms per eigh).
 template <int KK>
-__global__ __launch_bounds__(256) void rank2k_stream_fixed_kernel(double* __restrict__ C, int m, int ld,
-                                                                  const double* __restrict__ Up,
-                                                                  const double* __restrict__ Zp, int ldp, double alpha,
-                                                                  int upper_only) {
+__global__ __launch_bounds__(256) void rank2k_stream_fixed_kernel(Rank2kStreamArgs a) {
+    double* __restrict__ C = a.C;
+    const double* __restrict__ Up = a.Up;
+    const double* __restrict__ Zp = a.Zp;
+    const int m = a.m, ld = a.ld, ldp = a.ldp, upper_only = a.upper_only;
+    const double alpha = a.alpha;
     __shared__ double dl[RS_TR][RS_TC + 2];
     constexpr int KS = 2 * KK / 4;
     // upper_only: the caller reads the upper triangle only (symmetric-aware matvec of the tridiagonalisation): tiles
@@ -234,18 +266,20 @@ __global__ __launch_bounds__(256) void rank2k_stream_fixed_kernel(double* __rest
 #pragma unroll
     for (int q = 0; q < RS_TR / 4; ++q) {
         const int r = r0 + 4 * q + pr;
+        double2 v = cv[q];
         if (r < m && cidx < m) {
             double* p = C + (size_t)r * ld + cidx;
             const double d0 = dl[4 * q + pr][2 * pc], d1 = dl[4 * q + pr][2 * pc + 1];
             if (cidx + 1 < m) {
-                double2 v = cv[q];
                 v.x += alpha * d0;
                 v.y += alpha * d1;
                 *reinterpret_cast<double2*>(p) = v;
             } else {
-                p[0] = cv[q].x + alpha * d0;
+                v.x += alpha * d0;
+                p[0] = v.x;
             }
         }
+        if (q == 0 && a.seam_u && r == 0) rank2k_seam_row(a, cidx, v.x, v.y);      // (r == 0: uniform over the wavefront)
     }
 }
 
@@ -277,24 +311,36 @@ int launch_mirror_upper(sella_ctx* c, double* C, int m, int ld) {
     return SELLA_OK;
 }
 
+static int rank2k_stream_launch(sella_ctx* c, const Rank2kStreamArgs& a) {
+    const int m = a.m, kk = a.kk;
+    const double part = a.upper_only ? 0.5 : 1.0;
+    prof_begin(c, PROF_UPDATE, part * 16.0 * m * (double)m, part * 4.0 * kk * (double)m * m);
+    const dim3 grid((m + RS_TC - 1) / RS_TC, (m + RS_TR - 1) / RS_TR);
+    if (kk == 16 && c->opt.rank2k_fixed) SELLA_LAUNCH(c, rank2k_stream_fixed_kernel<16>, grid, dim3(256), 0, a);
+    else if (kk == 32 && c->opt.rank2k_fixed) SELLA_LAUNCH(c, rank2k_stream_fixed_kernel<32>, grid, dim3(256), 0, a);
+    else SELLA_LAUNCH(c, rank2k_stream_kernel, grid, dim3(256), 0, a);
+    prof_end(c);
+    HIPCHK(hipGetLastError());
+    return SELLA_OK;
+}
+
 int launch_rank2k_stream(sella_ctx* c, double* C, int m, int ld, const double* Up, const double* Zp, int ldp, int kk,
                          double alpha, bool upper_only) {
     if (m <= 0 || kk <= 0) return SELLA_OK;
     if ((ld & 1) || (reinterpret_cast<uintptr_t>(C) & 15)) return launch_sym_rank2k(c, C, m, ld, Up, Zp, ldp, kk, alpha);
-    const double part = upper_only ? 0.5 : 1.0;
-    prof_begin(c, PROF_UPDATE, part * 16.0 * m * (double)m, part * 4.0 * kk * (double)m * m);
-    const dim3 grid((m + RS_TC - 1) / RS_TC, (m + RS_TR - 1) / RS_TR);
-    const int uo = upper_only ? 1 : 0;
-    if (kk == 16 && c->opt.rank2k_fixed)
-        SELLA_LAUNCH(c, rank2k_stream_fixed_kernel<16>, grid, dim3(256), 0, C, m, ld, Up, Zp, ldp, alpha, uo);
-    else if (kk == 32 && c->opt.rank2k_fixed)
-        SELLA_LAUNCH(c, rank2k_stream_fixed_kernel<32>, grid, dim3(256), 0, C, m, ld, Up, Zp, ldp, alpha, uo);
-    else
-    SELLA_LAUNCH(c, rank2k_stream_kernel, grid, dim3(256), 0, C, m, ld, Up,
-                 Zp, ldp, kk, alpha);
-    prof_end(c);
-    HIPCHK(hipGetLastError());
-    return SELLA_OK;
+    const Rank2kStreamArgs a = {C, m, ld, Up, Zp, ldp, kk, alpha, upper_only ? 1 : 0, nullptr, nullptr, nullptr};
+    return rank2k_stream_launch(c, a);
+}
+
+int launch_rank2k_stream_seam(sella_ctx* c, double* C, int m, int ld, const double* Up, const double* Zp, int ldp, int kk,
+                              double alpha, const Rank2kSeam& seam, int* npart) {
+    if (m <= 0 || kk <= 0 || (ld & 1) || (reinterpret_cast<uintptr_t>(C) & 15) || !seam.u || !seam.d || !seam.partA) {
+        set_error("rank2k_stream_seam: needs a non-empty 16-byte aligned block and all seam outputs");
+        return SELLA_E_INVALID;
+    }
+    const Rank2kStreamArgs a = {C, m, ld, Up, Zp, ldp, kk, alpha, 0, seam.u, seam.d, seam.partA};
+    *npart = (m + RS_TC - 1) / RS_TC;
+    return rank2k_stream_launch(c, a);
 }
 
 int launch_sym_rank2k(sella_ctx* c, double* B, int n, int ld, const double* Up, const double* Zp, int ldp,
