@@ -2156,6 +2156,24 @@ static void plan_deflation(int N, double* D, double* zz, MergePlan& pl) {
     pl.nrot = out.nrot;
 }
 
+// Scale of a merge problem: the power of two nearest the largest magnitude m in a (na entries) and b (nb entries) where
+// that is below one; 1 for m >= 0.71, for zero and for non-finite input.  plan_deflation_core drops rho |z_i| (units of
+// the matrix) against 8 eps max(|D|max, |z|max) with a unit-norm z, which is LAPACK's threshold (dlaed2 behind dstedc's
+// scaling to unit max-norm) only for a matrix of norm one.  For larger norms it is the stricter of the two — less is
+// deflated than LAPACK would, nothing is lost, and the results stay what they have always been; for a norm of 2^-k it is
+// 2^k times looser, and k bits were lost.  So problems below one are brought up to one (exactly: a power of two) and
+// those above are left alone.  Exponent kept above -1000 so that the reciprocal is finite.
+static double scale_below_one(const double* a, int na, const double* b, int nb) {
+    double m = 0.0;
+    for (int i = 0; i < na; ++i) m = std::max(m, fabs(a[i]));
+    for (int i = 0; i < nb; ++i) m = std::max(m, fabs(b[i]));
+    if (!(m > 0.0) || !(m < 0.7071067811865476)) return 1.0;
+    int ex;
+    const double f = frexp(m, &ex);                    // m = f 2^ex, f in [0.5, 1)
+    if (f < 0.7071067811865476) --ex;
+    return ldexp(1.0, std::max(-1000, ex));
+}
+
 // Divide and conquer on the tridiagonal (d, e) (host copies, modified).  On exit wout holds the
 // ascending eigenvalues and W.Za the eigenvectors as rows in matching order.
 static int dc_solve(EighWork& W, std::vector<double>& d, std::vector<double>& e, double* wout) {
@@ -2168,6 +2186,15 @@ static int dc_solve(EighWork& W, std::vector<double>& d, std::vector<double>& e,
     std::vector<std::vector<int>> by_height(maxdepth + 1);
     int root;
     build_tree(0, n, 0, maxdepth, nodes, by_height, &root);
+
+    // T of max-norm below one is scaled up to one (scale_below_one above; dstedc scales every T): the deflation thresholds
+    // suppose a matrix of norm one or more.  The eigenvalues are scaled back at the end.
+    const double tscale = scale_below_one(d.data(), n, e.data(), n - 1);
+    if (tscale != 1.0) {
+        const double inv = 1.0 / tscale;
+        for (int i = 0; i < n; ++i) d[i] *= inv;
+        for (int i = 0; i + 1 < n; ++i) e[i] *= inv;
+    }
 
     // tear: T = diag(T1', T2') + |e_m| u u^T at every internal node
     for (const Node& nd : nodes)
@@ -2428,7 +2455,7 @@ static int dc_solve(EighWork& W, std::vector<double>& d, std::vector<double>& e,
     // the same order std::stable_sort gives, at a tenth of its time)
     order.resize(n);
     ascending_order(vals.data(), n, order.data(), order_all.data());
-    for (int i = 0; i < n; ++i) wout[i] = vals[order[i]];
+    for (int i = 0; i < n; ++i) wout[i] = tscale * vals[order[i]];
     std::copy(order.begin(), order.end(), hidx);
     HIPCHK(hipMemcpyAsync(idxd, hidx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     SCHK(launch_gather_rows(c, cur, ld, idxd, n, n, nxt, ld));
@@ -2801,6 +2828,14 @@ static int eig_rank1_update(sella_ctx* c, EighWork& W, int nr, int n, int ld, do
     pl.lo = 0;
     pl.N = nr;
     pl.rho = fabs(sigma) * znorm2;
+    // as in dc_solve: a merge whose max(|D|max, rho) lies below one is brought up to one (exactly), the new spectrum
+    // multiplied back below
+    const double mscale = scale_below_one(D.data(), nr, &pl.rho, 1);
+    if (mscale != 1.0) {
+        const double inv = 1.0 / mscale;
+        for (int ip = 0; ip < nr; ++ip) D[ip] *= inv;
+        pl.rho *= inv;
+    }
     // ---- clusters of (numerically) equal eigenvalues: one Householder reflection per cluster --------
     // An approximate Hessian starts as lam0*I + low rank, so most of its spectrum is one value repeated
     // ~n times.  The pairwise Givens deflation below would walk through such a cluster with a chain of
@@ -2894,7 +2929,7 @@ static int eig_rank1_update(sella_ctx* c, EighWork& W, int nr, int n, int ld, do
     std::vector<int> order(nr), order_tmp(nr);
     ascending_order(nv.data(), nr, order.data(), order_tmp.data());
     if (neg) std::reverse(order.begin(), order.end());
-    for (int i = 0; i < nr; ++i) w[i] = neg ? -nv[order[i]] : nv[order[i]];
+    for (int i = 0; i < nr; ++i) w[i] = mscale * (neg ? -nv[order[i]] : nv[order[i]]);
     std::copy(order.begin(), order.end(), hidx);
     HIPCHK(hipMemcpyAsync(idxd, hidx, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     const double tt4 = now();

@@ -12,7 +12,7 @@ def check(ctx, A, tol=5e-13):
     w, V, Vt = ctx.eigh(ctx.upload(A))
     Vn, Vtn = V.numpy(), Vt.numpy()
     wr = np.linalg.eigvalsh(A)
-    scale = max(1.0, np.abs(wr).max())
+    scale = np.abs(wr).max() or 1.0                     # the norm of A itself (2-norm); 1 for the zero matrix only
     assert np.all(np.diff(w) >= 0)
     np.testing.assert_allclose(w, wr, atol=tol * scale * n ** 0.5)
     assert np.abs(A @ Vn - Vn * w).max() <= tol * scale * n
@@ -166,7 +166,7 @@ def _rank1_check(ctx, D, w, rho, tol=2e-14):
     lam, Ut = ctx.rank1_eig(D, w, rho)
     M = np.diag(D) + rho * np.outer(w, w)
     ref = np.linalg.eigvalsh(M)
-    scale = max(1.0, np.abs(ref).max())
+    scale = np.abs(ref).max() or 1.0
     np.testing.assert_allclose(lam, ref, atol=tol * scale, rtol=0)
     # strict interlacing D_j < lam_j < D_{j+1}: what the Gu/Eisenstat weights rely on
     assert np.all(lam >= D) and np.all(lam[:-1] <= D[1:])
