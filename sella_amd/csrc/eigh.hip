@@ -212,6 +212,7 @@ struct TrdGemvArgs {
     double* taus; double* evec; double* colscal;
     const double* Wp; const double* Vp; int ldp, i;   // panel rows appended to the matvec: exact W_p.v, V_p.v
     double* cdots;
+    int nslot, desc;            // NCH > 0: row pairs of the launch; desc: the workgroups take them from the far end (see below)
 };
 
 // K2.  wraw = A22 v for the reflector v = [1, scale*u] of column j (same block-cooperative streaming
@@ -226,11 +227,22 @@ struct TrdGemvArgs {
 // compiler cannot keep conditional loads in flight across the back edge): three dependent memory round trips per launch at
 // 3N = 3072 on top of the one for the partials, in a kernel whose whole life is 5 - 12 us.  Same expressions in the same
 // order: bit-identical results.
+// NCH > 0 and a.desc: workgroup b of a grid rounded up to G8 groups of eight takes slot q = (G8 - 1 - b/8) * 8 + (b & 7)
+// instead of slot b: the same row pairs on the same XCDs (b & 7 is kept), visited from the far end, so that what the L2s
+// hold at the end of one column's pass is what the next column's pass starts with (see the launch).  A workgroup whose slot
+// lies beyond the last row pair has nothing to do.  Everything below is written in terms of the slot.
 template <int NCH>
 __global__ __launch_bounds__(256) void trd_gemv_kernel(TrdGemvArgs a) {
     __shared__ double red[4][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int row0 = blockIdx.x * 2 - a.pad;              // local row of this workgroup's first row (may be < 0)
+    int q = blockIdx.x;
+    if constexpr (NCH > 0) {
+        if (a.desc) {
+            q = ((int)(gridDim.x >> 3) - 1 - (q >> 3)) * 8 + (q & 7);
+            if (q >= a.nslot) return;
+        }
+    }
+    const int row0 = q * 2 - a.pad;                   // local row of this workgroup's first row (may be < 0)
     const int mtot = a.m + 2 * a.i;
     const int oc = a.o - a.shift;                     // even absolute column of local column 0
     const double2* arow[2];
@@ -347,8 +359,8 @@ __global__ __launch_bounds__(256) void trd_gemv_kernel(TrdGemvArgs a) {
                 a.cdots[TRD_NBMAX + rr - a.m - a.i] = res;
             }
         }
-        a.partB[blockIdx.x] = p;
-        if (blockIdx.x == 0) {
+        a.partB[q] = p;
+        if (q == 0) {
             a.taus[a.j] = tau;
             a.evec[a.j] = beta;
             a.colscal[0] = tau;
@@ -2464,6 +2476,21 @@ static int dc_solve(EighWork& W, std::vector<double>& d, std::vector<double>& e,
     return SELLA_OK;
 }
 
+// The matvec of the blocked chain where the trailing block no longer fits the eight L2s (8 m^2 > TRD_L2_BYTES; 24 MiB of
+// the 32): the lazily updated block is re-read unchanged by every column of a panel, but workgroups are dispatched in
+// ascending order and a cyclic sweep over more than the cache holds re-uses next to nothing.  Every second column (even j)
+// therefore takes the row pairs from the far end (trd_gemv_kernel, a.desc), so a pass starts with the rows the pass before it
+// ended with, on the same XCDs.  Only which workgroup takes which row pair changes: every sum is formed from the same
+// operands in the same order.  Measured in profiles/trd_gemv_l2.md (a split into resident and non-temporally streamed rows
+// was measured there too and lost).  Where the block fits, geometry and order are the ascending ones throughout.
+// Overridable per call for tests and sweeps: SELLA_EIGH_L2_BYTES (0: ascending everywhere), SELLA_EIGH_L2_SWEEP (0: same).
+static constexpr double TRD_L2_BYTES = 24.0 * 1024 * 1024;
+static constexpr int TRD_L2_SWEEP = 1;
+static double env_number(const char* name, double dflt) {
+    const char* s = getenv(name);
+    return (s && *s) ? atof(s) : dflt;
+}
+
 // Blocked tridiagonalisation of W.A (destroyed; reflector tails are left in its rows).
 static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec) {
     sella_ctx* c = W.c;
@@ -2492,6 +2519,8 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
     double* colscal2[2] = {colscal, partB2[1] + maxblkB + 8};
     double* wraw2[2] = {wraw, W.vec + (size_t)V_WRAW2 * ld};
     const int upd_max = (int)c->opt.eigh_upd_max;
+    const double l2_bytes = env_number("SELLA_EIGH_L2_BYTES", TRD_L2_BYTES);
+    const bool l2_sweep = l2_bytes > 0.0 && env_number("SELLA_EIGH_L2_SWEEP", TRD_L2_SWEEP) != 0.0;
     int cur = 0, nblkA_prev = 0, nblkB_prev = 0;
     // symmetric-aware matvec for trailing blocks of at least `eigh_symv_min` rows (0: never)
     const int symv_min = (int)c->opt.eigh_symv_min;
@@ -2649,6 +2678,7 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
             // are dummies.
             ga.pad = o - (o / 16) * 16;
             int nblkB = (ga.pad + m + 2 * i + 1) / 2;
+            ga.nslot = nblkB; ga.desc = 0;
             if (panel_symv) {
                 // large trailing block: upper triangle only, partial sums added up by a second (small) kernel
                 TrdSymvArgs sa;
@@ -2675,12 +2705,15 @@ static int tridiagonalise(EighWork& W, double* taus, double* dvec, double* evec)
                 prof_begin(c, PROF_TRD_GEMV, 8.0 * m * (double)m, 2.0 * m * (double)m);
                 const int n2g = (m + ga.shift + 1) >> 1;                // 16-byte pieces per row (as in the kernel)
                 const int nch = c->opt.eigh_gemv_flat ? (n2g + 255) / 256 : 1 << 30;
-                if (nch <= 2) SELLA_LAUNCH(c, trd_gemv_kernel<2>, dim3(nblkB), dim3(256), 0, ga);
-                else if (nch <= 4) SELLA_LAUNCH(c, trd_gemv_kernel<4>, dim3(nblkB), dim3(256), 0, ga);
-                else if (nch <= 6) SELLA_LAUNCH(c, trd_gemv_kernel<6>, dim3(nblkB), dim3(256), 0, ga);
-                else if (nch <= 8) SELLA_LAUNCH(c, trd_gemv_kernel<8>, dim3(nblkB), dim3(256), 0, ga);
-                else if (nch <= 10) SELLA_LAUNCH(c, trd_gemv_kernel<10>, dim3(nblkB), dim3(256), 0, ga);
-                else SELLA_LAUNCH(c, trd_gemv_kernel<0>, dim3(nblkB), dim3(256), 0, ga);
+                // (the loop form never descends: it is the form the flat ones are compared with)
+                ga.desc = l2_sweep && nch <= 10 && 8.0 * m * (double)m > l2_bytes && !(j & 1);
+                const int gridB = ga.desc ? (nblkB + 7) / 8 * 8 : nblkB;
+                if (nch <= 2) SELLA_LAUNCH(c, trd_gemv_kernel<2>, dim3(gridB), dim3(256), 0, ga);
+                else if (nch <= 4) SELLA_LAUNCH(c, trd_gemv_kernel<4>, dim3(gridB), dim3(256), 0, ga);
+                else if (nch <= 6) SELLA_LAUNCH(c, trd_gemv_kernel<6>, dim3(gridB), dim3(256), 0, ga);
+                else if (nch <= 8) SELLA_LAUNCH(c, trd_gemv_kernel<8>, dim3(gridB), dim3(256), 0, ga);
+                else if (nch <= 10) SELLA_LAUNCH(c, trd_gemv_kernel<10>, dim3(gridB), dim3(256), 0, ga);
+                else SELLA_LAUNCH(c, trd_gemv_kernel<0>, dim3(gridB), dim3(256), 0, ga);
                 prof_end(c);
             }
             c->prof = prof_all;
