@@ -511,19 +511,55 @@ int sella_emt_cell_hvp(sella_ctx* ctx, int n, const double* pos, const double* p
                        const double* shifts, const double* cell, double rc, double acut, double cutoff, double beta,
                        const double* V, int k, double* HV);
 
+/* ---- pair potentials (Morse, Lennard-Jones): the potential of tests/integration/test_morse_cluster.py ------------- */
+/* Energy and gradient of E = 1/2 sum over the ordered visits (i <- j, image s) of phi(r), r = |x_j + S_s - x_i|
+ * (csrc/pair.hip: one pass, one workgroup per atom, sums reduced in-block — the same bits from call to call).
+ * pos (n x 3); form and params: 0 Morse, phi = D (1 - e^{-a (r - r0)})^2 - D, params D, a, r0;
+ *                               1 Lennard-Jones, phi = 4 eps ((sigma / r)^12 - (sigma / r)^6), params eps, sigma;
+ * shifts (nshift x 3): lattice translations of the periodic images to include (with the zero vector), cells narrower than
+ * 2 rcut included; rcut > 0: the shifted-force form phi(r) - phi(rcut) - phi'(rcut)(r - rcut) inside rcut and zero beyond
+ * (energy and force continuous there, phi'' not); rcut <= 0: no cutoff — plain phi over all pairs, allowed for nshift = 1
+ * only.  A visit of an atom to its own image adds 1/2 phi to the energy and to the virial, nothing to forces or Hessian.
+ * Outputs: *energy, grad (n x 3) = dE/dx.  Limits (also of sella_calc_pair_create): n < 2^24 atoms and nshift <= 127
+ * images.  SELLA_E_INVALID beyond them, for a null pointer, n or nshift <= 0, another form, parameters, shifts or rcut
+ * that are not finite, sigma <= 0, or no cutoff with nshift > 1.                                                      */
+int sella_pair_eval(sella_ctx* ctx, int n, const double* pos, int form, const double* params, int nshift,
+                    const double* shifts, double rcut, double* energy, double* grad);
+/* The same evaluation plus the virial in the same pass.  virial6 (6): the convention of sella_emt_eval_stress, W_ab =
+ * dE/d eps_ab = 1/2 sum over the visits of (phi'/r) d_a d_b, Voigt order (xx, yy, zz, yz, xz, xy), eV; stress =
+ * virial6 / V.  *energy and grad are bit-for-bit those of sella_pair_eval.                                          */
+int sella_pair_eval_stress(sella_ctx* ctx, int n, const double* pos, int form, const double* params, int nshift,
+                           const double* shifts, double rcut, double* energy, double* grad, double* virial6);
+/* The analytic Hessian d2E/dx2 of the same potential, arguments and limits as for sella_pair_eval.
+ *   hessian: out (3n x 3n, allocated by the caller) is overwritten and stays on the device; exactly symmetric.  Row block
+ *     i holds -K on (i, j) and sum K on (i, i), K = phi'' u u^T + (phi'/r)(I - u u^T) summed over the images of j; no
+ *     temporary storage.
+ *   hvp: HV[q] = H V[q] for k vectors, V and HV (k x 3n) host arrays with one vector per row; no 3n x 3n storage.  The
+ *     visits of the geometry (neighbour, direction, phi'/r, phi'' - phi'/r: 44 bytes each) are built once per call and the
+ *     vectors taken through them 16 at a time.
+ * A wrong shape of `out`, k <= 0 or a null pointer: SELLA_E_INVALID.                                                */
+int sella_pair_hessian(sella_ctx* ctx, int n, const double* pos, int form, const double* params, int nshift,
+                       const double* shifts, double rcut, sella_mat out);
+int sella_pair_hvp(sella_ctx* ctx, int n, const double* pos, int form, const double* params, int nshift,
+                   const double* shifts, double rcut, const double* V, int k, double* HV);
+
 /* ---- calculators that live in the library, and the finite-difference Hessian on top of one ----------------- */
 /* sella/peswrapper.py:413-418 evaluates energy and forces through `atoms.calc`; for a calculator implemented HERE that
  * boundary can be crossed without the host language: sella_calc_eval(calc, x, &f, g) -> energy and gradient dE/dx.
  *   model: f(x) = 1/2 x^T A x + c/3 sum_j (u_j . x)^3, A (n x n resident), U (nu x n host, copied);
- *   emt:   the arguments of sella_emt_eval, fixed at creation (n = 3 natoms).                                        */
+ *   emt:   the arguments of sella_emt_eval, fixed at creation (n = 3 natoms);
+ *   pair:  the arguments of sella_pair_eval, fixed at creation (n = 3 natoms; parameters and shifts resident).      */
 typedef struct sella_calc sella_calc;
 int sella_calc_model_create(sella_ctx* ctx, sella_mat A, const double* U, int nu, int n, double c, sella_calc** calc);
 int sella_calc_emt_create(sella_ctx* ctx, int natoms, const double* par, int nshift, const double* shifts, double rc,
                           double acut, double cutoff, double beta, sella_calc** calc);
+int sella_calc_pair_create(sella_ctx* ctx, int natoms, int form, const double* params, int nshift, const double* shifts,
+                           double rcut, sella_calc** calc);
 int sella_calc_eval(sella_calc* calc, const double* x, double* energy, double* grad);
 /* Second derivatives at x: the Hessian into out (n x n, allocated by the caller, stays on the device), and its products
  * HV[q] = H V[q] with k host vectors (V, HV: k x n, one vector per row).  emt: sella_emt_hessian / sella_emt_hvp on the
- * calculator's resident constants, bit for bit; model: A + 2 c sum_j (u_j . x) u_j u_j^T.  Neither counts as a force
+ * calculator's resident constants, bit for bit; pair: sella_pair_hessian / sella_pair_hvp, bit for bit; model:
+ * A + 2 c sum_j (u_j . x) u_j u_j^T.  Neither counts as a force
  * call (sella_calc_ncalls is unchanged).  Wrong shapes: SELLA_E_INVALID.                                              */
 int sella_calc_hessian(sella_calc* calc, const double* x, sella_mat out);
 int sella_calc_hvp(sella_calc* calc, const double* x, const double* V, int k, double* HV);
@@ -548,8 +584,10 @@ int sella_fd_destroy(sella_fd* fd);
 /* The same operator in closed form, for a calculator that has its second derivatives (sella_calc_hvp): H v exactly, no
  * displacement, no force call (sella_calc_ncalls is unchanged).  What depends on the geometry x0 is built ONCE at creation
  * and stays resident in an allocation of the operator's own — emt: one density pass and the second derivatives of the
- * embedding functions (positions, densities, neighbour lists); model: the rows 2 c (u_j . x0) u_j — so a product is two
- * launches on one device vector (emt; model: two row-panel matvecs) plus one that spreads the m free entries idx[0..m)
+ * embedding functions (positions, densities, neighbour lists); pair: the visits of every atom in the order of the sweep, with
+ * the neighbour, the unit vector, phi'/r and phi'' - phi'/r of each (one counting and one filling pass; a product then
+ * evaluates no exp, sqrt or division); model: the rows 2 c (u_j . x0) u_j — so a product is two
+ * launches on one device vector (emt; pair: one; model: two row-panel matvecs) plus one that spreads the m free entries idx[0..m)
  * (ascending; NULL: all n) over the full space.  The product is (H vfull)[idx] with vfull zero on the pinned coordinates.
  *   sella_hvp_matvec     the sella_matvec_fn form with HOST vectors (upload, the device product, download, wait): the
  *                        operator also serves the unchanged sella_davidson as its callback.
@@ -595,7 +633,7 @@ int sella_fd_destroy(sella_fd* fd);
  * workgroup, a row's result independent of its slot, of the number of rows and of the other rows) are counted and not
  * recorded, sella_hvp_diag returns diag(H_xx)[idx] followed by the mc diagonal entries of J^T (H_CC + P) J + G (from one
  * block product of unit rows that is not counted), and both Davidson drivers take it unchanged.  SELLA_E_INVALID: a null
- * pointer (P excepted), a calculator that is not the EMT kind, n != sella_calc_dim, mc < 1 or mc > 9, idx not ascending or
+ * pointer (P excepted), a calculator that is not the EMT kind (the message names the kind), n != sella_calc_dim, mc < 1 or mc > 9, idx not ascending or
  * out of range, a singular cell, a shift of the calculator that is no lattice translation of `cell`.                       */
 typedef struct sella_hvp sella_hvp;
 int sella_hvp_create(sella_calc* calc, int n, const double* x0, const int* idx, int m, sella_hvp** op);

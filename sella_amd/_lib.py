@@ -116,6 +116,7 @@ SIGNATURES = {
     'sella_calc_model_create': (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_double, POINTER(c_void_p)]),
     'sella_calc_emt_create': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_double, c_double,
                                       POINTER(c_void_p)]),
+    'sella_calc_pair_create': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_double, POINTER(c_void_p)]),
     'sella_calc_eval': (c_int, [c_void_p, c_void_p, POINTER(c_double), c_void_p]),
     'sella_calc_hessian': (c_int, [c_void_p, c_void_p, c_int]),
     'sella_calc_hvp': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -201,6 +202,12 @@ SIGNATURES = {
                                        c_double, c_double, c_int]),
     'sella_emt_cell_hvp': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double,
                                    c_double, c_double, c_void_p, c_int, c_void_p]),
+    'sella_pair_eval': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double_p, c_void_p]),
+    'sella_pair_eval_stress': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double_p,
+                                       c_void_p, c_void_p]),
+    'sella_pair_hessian': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_int]),
+    'sella_pair_hvp': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_void_p, c_int,
+                               c_void_p]),
     'sella_prof_enable': (c_int, [c_void_p, c_int]),
     'sella_prof_reset': (c_int, [c_void_p]),
     'sella_prof_get': (c_int, [c_void_p, c_int, POINTER(c_long), c_double_p, c_double_p, c_double_p]),

@@ -8,7 +8,9 @@ image; when `ase` imports, its own classes are used instead and these are bypass
               ase.optimize.optimize.Optimizer (sella/optimize/optimize.py:10,177)
   calculators on the far side of the calculator boundary, for tests and benchmarks:
               QuadraticCubicModel (SURVEY.md §8d model PES), MorseCluster
-              (tests/integration/test_morse_cluster.py), PairLJ.
+              (tests/integration/test_morse_cluster.py), PairLJ — O(N^2) NumPy on the host, the yardsticks of
+              Morse and LennardJones, the same pair potentials on the device (csrc/pair.hip) with stress, Hessian,
+              Hessian-vector products and a library form.
 """
 import sys
 import time
@@ -695,6 +697,104 @@ class EMT(Calculator):
                                                      S['acut'], S['cutoff'], self._BETA))
             self._devcalc = hit
         return hit[1]
+
+
+class _DevicePairPotential(Calculator):
+    """A pair potential E = 1/2 sum over ordered pairs of phi(r) on the device (csrc/pair.hip), with everything a
+    calculator of the library has: energy and forces, the virial (`get_stress`), the analytic Hessian and its products
+    (`get_hessian`, `get_device_hessian`, `hessian_vector_product`), and its library form (`device_calculator()`:
+    whole searches, cohorts, the finite-difference and the exact Hessian-vector operators).
+
+    rcut=None sums plain phi over all pairs and is for systems without a periodic direction (ValueError otherwise).  With
+    a cutoff the pair function is the shifted-force form phi(r) - phi(rcut) - phi'(rcut) (r - rcut) inside rcut and zero
+    beyond, as `PeriodicMorse` uses; periodic directions are an explicit image sum (`EMT.image_shifts`), so cells narrower
+    than 2 rcut work, up to 127 images.  One parameter set per calculator.  There are no second derivatives with respect
+    to the cell: `get_cell_hessian` and `cell_hessian_vector_product` raise NotImplementedError."""
+    _form = None
+
+    def __init__(self, params, rcut):
+        super().__init__()
+        self._params = np.array(params, dtype=np.float64)
+        self.rcut = None if rcut is None else float(rcut)
+        if not np.all(np.isfinite(self._params)) or (self.rcut is not None and not (np.isfinite(self.rcut) and self.rcut > 0.0)):
+            raise ValueError(f'{type(self).__name__}: the parameters must be finite and rcut positive (or None)')
+        self._setup = None
+
+    def _prepare(self, atoms):
+        key = (len(atoms), np.asarray(atoms.cell, dtype=float).tobytes(), tuple(bool(p) for p in atoms.pbc))
+        if self._setup is None or self._setup[0] != key:
+            if self.rcut is None:
+                if np.any(atoms.pbc):
+                    raise ValueError(f'{type(self).__name__}: a periodic system needs a cutoff (rcut=None sums over all pairs)')
+                shifts = np.zeros((1, 3))
+            else:
+                shifts = EMT.image_shifts(atoms.cell, atoms.pbc, self.rcut)
+            self._setup = (key, dict(natoms=len(atoms), shifts=np.ascontiguousarray(shifts)))
+            self._key = None                       # results cached for the old cell are stale
+            self._drop_hessian()
+
+    def _get(self, atoms, stress=False):
+        self._prepare(atoms)
+        return super()._get(atoms, stress)
+
+    def _pair_args(self, pos):
+        if self._setup is None:
+            raise RuntimeError(f'{type(self).__name__}: no atoms seen yet (evaluate through an Atoms object first)')
+        return pos, self._form, self._params, self._setup[1]['shifts'], self.rcut
+
+    def energy_and_gradient(self, pos):
+        from .device import get_context
+        return get_context().pair_eval(*self._pair_args(pos))
+
+    def energy_gradient_virial(self, pos):
+        from .device import get_context
+        return get_context().pair_eval_stress(*self._pair_args(pos))
+
+    def device_hessian(self, pos):
+        """The analytic Hessian (csrc/pair.hip: the pair blocks K = phi'' u u^T + (phi'/r)(I - u u^T) per atom)."""
+        from .device import get_context
+        return get_context().pair_hessian(*self._pair_args(pos))
+
+    def hessian_products(self, pos, V):
+        from .device import get_context
+        return get_context().pair_hvp(*self._pair_args(pos), V)
+
+    library_form = True
+
+    def device_calculator(self):
+        """This potential, for the cell it was last set up for, as a calculator inside the library
+        (`sella_calc_pair_create`); None before the first evaluation."""
+        if self._setup is None:
+            return None
+        hit = getattr(self, '_devcalc', None)
+        if hit is None or hit[0] is not self._setup:
+            from .device import DeviceCalculator, get_context
+            S = self._setup[1]
+            hit = (self._setup, DeviceCalculator.pair(get_context(), S['natoms'], self._form, self._params, S['shifts'],
+                                                      self.rcut))
+            self._devcalc = hit
+        return hit[1]
+
+
+class Morse(_DevicePairPotential):
+    """phi = D (1 - exp(-a (r - r0)))^2 - D on the device: `MorseCluster`'s function with rcut=None, `PeriodicMorse`'s
+    shifted-force form with a cutoff (there under the minimum image, here as an image sum)."""
+    _form = 'morse'
+
+    def __init__(self, D=1.0, a=1.0, r0=1.0, rcut=None):
+        super().__init__((D, a, r0), rcut)
+        self.D, self.a, self.r0 = float(D), float(a), float(r0)
+
+
+class LennardJones(_DevicePairPotential):
+    """phi = 4 eps ((sigma / r)^12 - (sigma / r)^6) on the device: `PairLJ`'s function with rcut=None."""
+    _form = 'lj'
+
+    def __init__(self, eps=1.0, sigma=1.0, rcut=None):
+        super().__init__((eps, sigma), rcut)
+        if not self._params[1] > 0.0:
+            raise ValueError('LennardJones: sigma must be positive')
+        self.eps, self.sigma = float(eps), float(sigma)
 
 
 class PairLJ(Calculator):

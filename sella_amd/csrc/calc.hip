@@ -6,9 +6,10 @@
 //
 //   sella_calc_model_*   f(x) = 1/2 x^T A x + c/3 sum_j (u_j . x)^3, A resident (the model PES of SURVEY.md section 8d)
 //   sella_calc_emt_*     effective-medium theory (emt.hip, sella_emt_eval)
+//   sella_calc_pair_*    a Morse or Lennard-Jones pair potential (pair.hip, sella_pair_eval)
 //   sella_fd_*           H v ~ (g(x0 + eta v^) - g0) / eta (or the central form), seen through a selection of free
 //                        coordinates; every product is remembered as a secant pair for the Hessian update afterwards
-//   sella_hvp_*          H v in closed form (EMT: emt_hessian.hip; model: A v + sum_j 2 c (u_j . x0)(u_j . v) u_j) through the
+//   sella_hvp_*          H v in closed form (EMT: emt_hessian.hip; pair: pair.hip; model: A v + sum_j 2 c (u_j . x0)(u_j . v) u_j) through the
 //                        same selection, on a state built once at x0 and owned by the operator: device vector in, device
 //                        vector out, no host wait per product (the third operator kind of sella_davidson, davidson.hip);
 //                        the pairs are recorded on the device.  Not force calls.  The same for the rows of a device panel
@@ -16,6 +17,7 @@
 //                        A second kind (sella_hvp_create_cell, EMT only): the Hessian of positions and cell in the
 //                        coordinates [x; p] of a cell run, through the same entries
 #include "emt.h"
+#include "pair.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,7 +27,7 @@ using namespace sella;
 
 struct sella_calc {
     sella_ctx* c = nullptr;
-    int kind = 0;                     // 0 model, 1 EMT
+    int kind = 0;                     // 0 model, 1 EMT, 2 pair potential
     int n = 0;
     long ncalls = 0;
     // model
@@ -38,7 +40,11 @@ struct sella_calc {
     std::vector<double> par, shifts;
     double rc = 0, acut = 0, cutoff = 0, beta = 0;
     std::vector<double> work;
-    double* dconst = nullptr;         // EMT: parameter table + shift vectors, resident; model: the rows u_j (nu x ld)
+    // pair potential (natoms, nshift, shifts as for EMT)
+    int form = 0;
+    PairPot pot = {};
+    double* dconst = nullptr;         // EMT: parameter table + shift vectors, resident; model: the rows u_j (nu x ld);
+                                      // pair: the parameters as given (3 doubles) + shift vectors
     size_t dconst_bytes = 0;
 };
 
@@ -201,6 +207,15 @@ int sella::calc_queue(sella_calc* k, const double* x, double** g_dev, double** a
         *naux = k->natoms;
         return SELLA_OK;
     }
+    if (k->kind == 2) {
+        double *dea, *dgr;
+        SCHK(pair_queue(c, k->natoms, x, k->form, k->pot, k->nshift, k->shifts.data(), k->dconst ? k->dconst + 3 : nullptr, &dea,
+                        &dgr, false));
+        *g_dev = dgr;
+        *aux_dev = dea;
+        *naux = k->natoms;
+        return SELLA_OK;
+    }
     const int n = k->n, ld = round_up(n, 8), nu = k->nu;
     Mat* A = mat_get(c, k->A);
     if (!A) return SELLA_E_INVALID;
@@ -220,7 +235,7 @@ int sella::calc_queue(sella_calc* k, const double* x, double** g_dev, double** a
 }
 
 double sella::calc_finish(sella_calc* k, const double* x, const double* aux) {
-    if (k->kind == 1) {
+    if (k->kind == 1 || k->kind == 2) {
         double e = 0.0;
         for (int i = 0; i < k->natoms; ++i) e += aux[i];
         return e;
@@ -258,6 +273,34 @@ extern "C" int sella_calc_emt_create(sella_ctx* c, int natoms, const double* par
     return SELLA_OK;
 }
 
+// A pair potential (pair.hip): form 0 Morse (params D, a, r0), 1 Lennard-Jones (params eps, sigma); rcut <= 0: no cutoff, for a
+// system without periodic images only.  The parameters as given and the shifts stay resident.
+extern "C" int sella_calc_pair_create(sella_ctx* c, int natoms, int form, const double* params, int nshift, const double* shifts,
+                                      double rcut, sella_calc** out) {
+    PairPot pot;
+    const char* bad = (!c || !out) ? "invalid arguments" : pair_pot_make(natoms, form, params, nshift, shifts, rcut, &pot);
+    if (bad) {
+        set_error("calc_pair: %s", bad);
+        return SELLA_E_INVALID;
+    }
+    sella_calc* k = new sella_calc();
+    k->c = c; k->kind = 2; k->n = 3 * natoms; k->natoms = natoms; k->nshift = nshift;
+    k->form = form; k->pot = pot;
+    k->shifts.assign(shifts, shifts + (size_t)3 * nshift);
+    const double par3[3] = {params[0], params[1], form == PAIR_MORSE ? params[2] : 0.0};
+    k->dconst_bytes = ((size_t)3 + (size_t)3 * nshift) * sizeof(double);
+    if (dev_alloc(c, k->dconst_bytes, &k->dconst) == SELLA_OK) {
+        int st = h2d_async(c, k->dconst, par3, sizeof(par3));
+        if (st == SELLA_OK) st = h2d_async(c, k->dconst + 3, shifts, (size_t)3 * nshift * sizeof(double));
+        if (st == SELLA_OK) st = stream_wait(c);
+        if (st != SELLA_OK) { dev_free(c, k->dconst, k->dconst_bytes); k->dconst = nullptr; }
+    } else {
+        k->dconst = nullptr;
+    }
+    *out = k;
+    return SELLA_OK;
+}
+
 // energy and gradient dE/dx at x (n entries)
 extern "C" int sella_calc_eval(sella_calc* k, const double* x, double* f, double* g) {
     if (!k || !x || !f || !g) return SELLA_E_INVALID;
@@ -285,6 +328,9 @@ extern "C" int sella_calc_hessian(sella_calc* k, const double* x, sella_mat out)
     if (k->kind == 1)
         return emt_hessian_resident(c, k->natoms, x, k->par.data(), k->nshift, k->shifts.data(), k->dconst, k->rc, k->acut,
                                     k->cutoff, k->beta, out);
+    if (k->kind == 2)
+        return pair_hessian_resident(c, k->natoms, x, k->form, k->pot, k->nshift, k->shifts.data(),
+                                     k->dconst ? k->dconst + 3 : nullptr, out);
     const int n = k->n, nu = k->nu, ld = round_up(n, 8);
     Mat *A = mat_get(c, k->A), *H = mat_get(c, out);
     if (!A) {
@@ -323,6 +369,8 @@ extern "C" int sella_calc_hvp(sella_calc* k, const double* x, const double* V, i
     if (k->kind == 1)
         return emt_hvp_resident(c, k->natoms, x, k->par.data(), k->nshift, k->shifts.data(), k->dconst, k->rc, k->acut,
                                 k->cutoff, k->beta, V, nv, HV);
+    if (k->kind == 2)
+        return pair_hvp_resident(c, k->natoms, x, k->form, k->pot, k->nshift, k->shifts.data(), V, nv, HV);
     const int n = k->n, nu = k->nu, ld = round_up(n, 8);
     Mat* A = mat_get(c, k->A);
     if (!A) {
@@ -482,6 +530,7 @@ struct sella_hvp {
     int n = 0, m = 0, ld = 0, nb = 0;     // full dimension, the eigensolver's, row stride, workgroups of the scatter
     bool select = false;
     EmtHvpState emt;                      // EMT kind
+    PairHvpState pair;                    // pair kind
     // the kind of positions and cell (sella_hvp_create_cell): n = nx + mc and m = mx + mc, the mc cell parameters behind the
     // nx position coordinates (mx of them free: inv covers the positions); nb counts the workgroups of the positions
     bool cell = false;
@@ -508,6 +557,7 @@ static void hvp_release(sella_hvp* o) {
     (void)stream_sync_raw(c);
     if (o->cell) emt_hvp_state_destroy(c, &o->cemt.s);
     else if (o->calc->kind == 1) emt_hvp_state_destroy(c, &o->emt);
+    else if (o->calc->kind == 2) pair_hvp_state_destroy(c, &o->pair);
     for (double* p : o->chunks) dev_free(c, p, o->chunk_bytes);
     if (o->aux) dev_free(c, o->aux, o->aux_bytes);
     if (o->blk) dev_free(c, o->blk, o->blk_bytes);
@@ -567,6 +617,8 @@ extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const
     if (calc->kind == 1) {
         st = emt_hvp_state_create(c, calc->natoms, x0, calc->par.data(), calc->nshift, calc->shifts.data(), calc->dconst, calc->rc,
                                   calc->acut, calc->cutoff, calc->beta, &o->emt);
+    } else if (calc->kind == 2) {
+        st = pair_hvp_state_create(c, calc->natoms, x0, calc->form, calc->pot, calc->nshift, calc->shifts.data(), &o->pair);
     } else {
         if (nu > 0) {
             std::vector<double> S((size_t)nu * ld, 0.0);               // rows 2 c (u_j . x0) u_j, as sella_calc_hessian builds them
@@ -596,7 +648,9 @@ extern "C" int sella_hvp_create_cell(sella_calc* calc, int n, const double* x0, 
         return SELLA_E_INVALID;
     }
     if (calc->kind != 1) {
-        set_error("hvp cell operator: only the EMT calculator has second derivatives with respect to the cell");
+        static const char* const names[] = {"model", "EMT", "pair-potential"};
+        set_error("hvp cell operator: only the EMT calculator has second derivatives with respect to the cell, not the %s "
+                  "calculator (kind %d)", names[calc->kind], calc->kind);
         return SELLA_E_INVALID;
     }
     if (mc < 1 || mc > 9) {
@@ -647,6 +701,7 @@ int sella::hvp_device_apply(sella_hvp* o, const double* x, double* y) {
     const int n = o->n;
     SELLA_LAUNCHB(c, hvp_scatter_kernel, hvp_scatter_vb, 256, dim3(o->nb), dim3(256), 0, n, x, (const int*)o->inv, v, o->part);
     if (k->kind == 1) return emt_hvp_state_apply(c, o->emt, v, hv, o->part, o->nb, o->inv, y, flag);
+    if (k->kind == 2) return pair_hvp_state_apply(c, o->pair, v, hv, o->part, o->nb, o->inv, y, flag);
     Mat* A = mat_get(c, k->A);
     if (!A) {
         set_error("hvp operator: the model calculator's matrix A is gone");
@@ -722,6 +777,7 @@ int sella::hvp_device_apply_block(sella_hvp* o, const double* X, int ldx, int nh
         V = o->bstage;
     }
     if (k->kind == 1) return emt_hvp_state_apply_block(c, o->emt, V, ldv, nh, o->inv, Y, ldy);
+    if (k->kind == 2) return pair_hvp_state_apply_block(c, o->pair, V, ldv, nh, o->inv, Y, ldy);
     SCHK(launch_panel16(c, A->d, n, n, A->ld, V, nh, o->bhv, o->ld));
     if (k->nu > 0) SCHK(launch_panel16(c, k->dconst, k->nu, n, o->ld, V, nh, o->bt, o->ldt));
     SELLA_LAUNCHB(c, hvp_model_finish_block_kernel, hvp_model_finish_block_vb, 256, dim3(o->nb, nh), dim3(256), 0, n, k->nu, o->ld,
@@ -781,6 +837,8 @@ extern "C" int sella_hvp_diag(sella_hvp* o, double* diag) {
     }
     if (k->kind == 1) {
         SCHK(emt_hvp_state_diag(c, o->emt, o->inv, o->dy));
+    } else if (k->kind == 2) {
+        SCHK(pair_hvp_state_diag(c, o->pair, o->inv, o->dy));
     } else {
         Mat* A = mat_get(c, k->A);
         if (!A) {

@@ -1,6 +1,7 @@
 // emt.h — what the effective-medium-theory kernels share (emt.hip: energy, forces, virial; emt_hessian.hip: second
 // derivatives): the argument block, the in-block reduction, and the format of the per-thread neighbour lists the density
-// pass hands on.
+// pass hands on.  The sweep over the (neighbour, image) pairs of an atom (emt_pairs) stands here too: the pair-potential
+// kernels (pair.hip) walk the same pairs in the same order.
 #pragma once
 #include "internal.h"
 
@@ -47,6 +48,78 @@ constexpr int EMT_HCAP = 8;               // slots of a thread's neighbour list
 
 // a noted pair: atom index in the low 24 bits, image above (no division when it is taken up again)
 __device__ __forceinline__ int emt_pack(int j, int s) { return (s << 24) | j; }
+
+// The sweep over all (neighbour, image) pairs is split in two per thread: first the distance test alone over the thread's
+// pairs (t = tid, tid + 256, ...: no division, squared distance against a slightly widened cutoff), the few pairs inside
+// the cutoff noted in LDS; then the exponentials for those only.  Under 1 % of the pairs are neighbours, but with the
+// expensive branch inside the sweep every second wavefront iteration took it for some lane; deferred, a wavefront
+// pays for the largest number of neighbours any of its lanes found (2-3).  The terms are added per thread in the same
+// order as before — sums are bit-identical to the one-loop form.
+constexpr int EMT_LDS_ATOMS = 1024;       // up to this many atoms the positions are staged in LDS (structure of arrays)
+
+struct EmtStage {
+    double x[EMT_LDS_ATOMS], y[EMT_LDS_ATOMS], z[EMT_LDS_ATOMS];
+};
+
+// All pairs of this thread (t = s n + j = tid mod 256, in increasing t) through `heavy`, in two steps: the distance test alone
+// — image by image (s uniform: its shift sits in scalar registers), neighbours noted in hits[tid][..] — then the noted pairs.
+// A thread whose list fills up (never at EMT's cutoff and 256 threads) works it off and takes its remaining pairs
+// directly, in the same order; the count returned is then negative: the stored list is incomplete.
+template <bool STAGED, class Heavy>
+__device__ __forceinline__ int emt_pairs_impl(const EmtArgs& a, double xi, double yi, double zi, const EmtStage* st,
+                                              int (*hits)[EMT_HCAP + 1], Heavy heavy) {
+    const int tid = threadIdx.x, n = a.n;
+    const double cut2 = a.cutoff * a.cutoff * (1.0 + 1e-12);
+    const bool aligned = (n & 255) == 0;
+    auto first_j = [&](int s) { return aligned ? tid : (((tid - s * n) % 256) + 256) % 256; };
+    // (pos + shift) - x_i as in the terms themselves: the same rounding decides which pairs are neighbours
+    auto near = [&](int j, double shx, double shy, double shz) {
+        const double px = STAGED ? st->x[j] : a.pos[3 * j], py = STAGED ? st->y[j] : a.pos[3 * j + 1];
+        const double pz = STAGED ? st->z[j] : a.pos[3 * j + 2];
+        const double dx = px + shx - xi, dy = py + shy - yi, dz = pz + shz - zi;
+        return dx * dx + dy * dy + dz * dz <= cut2;
+    };
+    int nh = 0, rs = -1, rj = 0;
+    for (int s = 0; s < a.nshift; ++s) {
+        const double shx = a.shifts[3 * s], shy = a.shifts[3 * s + 1], shz = a.shifts[3 * s + 2];
+        if (rs >= 0) continue;                                     // (this thread's list is full: see below)
+        for (int j = first_j(s); j < n; j += 1024) {
+            bool in[4];                                            // four tests at a time: their loads are in flight together
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int ju = j + 256 * u;
+                in[u] = near(ju < n ? ju : j, shx, shy, shz) && ju < n;
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (in[u] && rs < 0) {
+                    if (nh == a.hcap) { rs = s; rj = j + 256 * u; }
+                    else hits[tid][nh++] = emt_pack(j + 256 * u, s);
+                }
+            }
+            if (rs >= 0) break;
+        }
+    }
+    for (int h = 0; h < nh; ++h) heavy(hits[tid][h]);
+    if (rs < 0) return nh;
+    for (int s = rs; s < a.nshift; ++s) {
+        const double shx = a.shifts[3 * s], shy = a.shifts[3 * s + 1], shz = a.shifts[3 * s + 2];
+        for (int j = (s == rs) ? rj : first_j(s); j < n; j += 256)
+            if (near(j, shx, shy, shz)) heavy(emt_pack(j, s));
+    }
+    return -1;
+}
+
+template <class Heavy>
+__device__ __forceinline__ int emt_pairs(const EmtArgs& a, double xi, double yi, double zi, EmtStage* st, int (*hits)[EMT_HCAP + 1],
+                                         Heavy heavy) {
+    if (a.n <= EMT_LDS_ATOMS) {
+        for (int j = threadIdx.x; j < a.n; j += 256) { st->x[j] = a.pos[3 * j]; st->y[j] = a.pos[3 * j + 1]; st->z[j] = a.pos[3 * j + 2]; }
+        __syncthreads();
+        return emt_pairs_impl<true>(a, xi, yi, zi, st, hits, heavy);
+    }
+    return emt_pairs_impl<false>(a, xi, yi, zi, st, hits, heavy);
+}
 
 }  // namespace
 

@@ -711,6 +711,55 @@ class Context:
                                             float(rc), float(acut), float(cutoff), float(beta), ptr(V), V.shape[0], ptr(HV)))
         return HV.reshape(shape)
 
+    # ---- pair potentials (Morse, Lennard-Jones) ------------------------------------------------------
+    def pair_eval(self, pos, form, params, shifts, rcut):
+        """(energy, gradient (n, 3)) of a pair potential (`sella_pair_eval`): form 'morse' (params D, a, r0) or 'lj'
+        (params eps, sigma), shifts (nshift, 3), rcut None (no cutoff: a system without periodic images) or the cutoff of
+        the shifted-force form."""
+        pos, form, params, shifts, rcut = _pair_args(pos, form, params, shifts, rcut)
+        n = pos.shape[0]
+        e = c_double(0.0)
+        grad = np.empty((n, 3))
+        check(_lib.lib().sella_pair_eval(self._h, n, ptr(pos), form, ptr(params), shifts.shape[0], ptr(shifts), rcut,
+                                         byref(e), ptr(grad)))
+        return e.value, grad
+
+    def pair_eval_stress(self, pos, form, params, shifts, rcut):
+        """(energy, gradient (n, 3), virial (6,)) from one device evaluation (`sella_pair_eval_stress`): energy and gradient
+        as `pair_eval`'s, the virial in the convention of `emt_eval_stress`."""
+        pos, form, params, shifts, rcut = _pair_args(pos, form, params, shifts, rcut)
+        n = pos.shape[0]
+        e = c_double(0.0)
+        grad = np.empty((n, 3))
+        virial = np.empty(6)
+        check(_lib.lib().sella_pair_eval_stress(self._h, n, ptr(pos), form, ptr(params), shifts.shape[0], ptr(shifts), rcut,
+                                                byref(e), ptr(grad), ptr(virial)))
+        return e.value, grad, virial
+
+    def pair_hessian(self, pos, form, params, shifts, rcut):
+        """The analytic Cartesian Hessian of a pair potential as a (3n x 3n) `DeviceMatrix` (`sella_pair_hessian`): exactly
+        symmetric, left on the device."""
+        pos, form, params, shifts, rcut = _pair_args(pos, form, params, shifts, rcut)
+        n = pos.shape[0]
+        out = self.zeros(3 * n, 3 * n)
+        try:
+            check(_lib.lib().sella_pair_hessian(self._h, n, ptr(pos), form, ptr(params), shifts.shape[0], ptr(shifts), rcut,
+                                                out.handle))
+        except Exception:
+            out.free()
+            raise
+        return out
+
+    def pair_hvp(self, pos, form, params, shifts, rcut, V):
+        """H V[q] for the rows of V (k, 3n) (or one vector (3n,)) without forming H (`sella_pair_hvp`); same shape as V."""
+        pos, form, params, shifts, rcut = _pair_args(pos, form, params, shifts, rcut)
+        n = pos.shape[0]
+        V, shape = _hvp_vectors(V, 3 * n)
+        HV = np.empty_like(V)
+        check(_lib.lib().sella_pair_hvp(self._h, n, ptr(pos), form, ptr(params), shifts.shape[0], ptr(shifts), rcut,
+                                        ptr(V), V.shape[0], ptr(HV)))
+        return HV.reshape(shape)
+
     # ---- profiling ---------------------------------------------------------------------------
     def prof_enable(self, on=True):
         check(_lib.lib().sella_prof_enable(self._h, int(bool(on))))
@@ -735,6 +784,25 @@ def _hvp_vectors(V, n):
     return np.ascontiguousarray(V), shape
 
 
+PAIR_FORMS = {'morse': (0, 3), 'lj': (1, 2)}          # name -> (the library's number, parameters)
+
+
+def _pair_args(pos, form, params, shifts, rcut):
+    """The arguments of the `sella_pair_*` entries as the library takes them: positions (n, 3), the form's number, its
+    parameters, shifts (nshift, 3) and the cutoff (0.0 for None).  Wrong shapes raise ValueError."""
+    if form not in PAIR_FORMS:
+        raise ValueError(f'pair potential form must be one of {sorted(PAIR_FORMS)}, got {form!r}')
+    number, npar = PAIR_FORMS[form]
+    pos = as_f64(pos)
+    if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] == 0:
+        raise ValueError(f'expected positions of shape (n, 3), got {pos.shape}')
+    params = as_f64(params, (npar,))
+    shifts = as_f64(shifts)
+    if shifts.ndim != 2 or shifts.shape[1] != 3 or shifts.shape[0] == 0:
+        raise ValueError(f'expected image shifts of shape (nshift, 3), got {shifts.shape}')
+    return pos, number, params, shifts, 0.0 if rcut is None else float(rcut)
+
+
 class DeviceCalculator:
     """A calculator that lives in the library (`sella_calc_*`, csrc/calc.hip): energy and gradient without a
     host-language frame, so that the finite-difference products of an iterative diagonalisation are library calls."""
@@ -756,6 +824,15 @@ class DeviceCalculator:
         h = c_void_p()
         check(_lib.lib().sella_calc_emt_create(ctx._h, int(natoms), ptr(par), shifts.shape[0], ptr(shifts), float(rc),
                                                float(acut), float(cutoff), float(beta), byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def pair(cls, ctx, natoms, form, params, shifts, rcut):
+        """A pair potential (`sella_calc_pair_create`): arguments as for `Context.pair_eval`."""
+        _, number, params, shifts, rcut = _pair_args(np.zeros((int(natoms), 3)), form, params, shifts, rcut)
+        h = c_void_p()
+        check(_lib.lib().sella_calc_pair_create(ctx._h, int(natoms), number, ptr(params), shifts.shape[0], ptr(shifts), rcut,
+                                                byref(h)))
         return cls(ctx, h)
 
     def eval(self, x):

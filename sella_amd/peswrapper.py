@@ -87,7 +87,9 @@ def _split_cons_subspace(drdx, tol_factor=1e-6):
                     register_selection(np.ascontiguousarray(eye[:, free]), free))
     Q, R, _ = qr(drdx.T, mode='full', pivoting=True, check_finite=False)
     diag = np.abs(np.diag(R))
-    ncons = int(np.sum(diag > tol_factor * diag[0])) if diag.size and diag[0] > 0 else 0
+    # A Jacobian that vanishes to rounding constrains nothing: rigid-body constraints seen from internal coordinates that
+    # are themselves invariant under translation and rotation (rows of ~1e-16: the relative rule alone counted them all)
+    ncons = int(np.sum(diag > tol_factor * diag[0])) if diag.size and diag[0] > 1e-12 else 0
     return Q[:, :ncons], Q[:, ncons:]
 
 
@@ -1001,6 +1003,10 @@ class InternalPES(PES):
             return np.zeros((0, n_int)), np.zeros((n_int, 0)), Unred, Unred
         drdxnred = cons_jac @ fac.BinvQ                    # dr/dx B^+ Q
         Vcons, Vfree = _split_cons_subspace(drdxnred)
+        if Vcons.shape[1] == 0:
+            # constraints the internal coordinates cannot violate (a fixed centre and orientation seen from bonds and
+            # angles): no constrained direction, and no multipliers from a Jacobian that is rounding noise
+            return np.zeros((0, n_int)), np.zeros((n_int, 0)), Unred, Unred
         return drdxnred @ Q.T, Unred @ Vcons, Unred, Unred @ Vfree
 
     def _calc_basis(self):
