@@ -50,6 +50,16 @@ __host__ __device__ inline void bordered_root_core(int mm, DAt Dat, BAt bat, dou
         if (j == 0) { lo = far; hi = fmin(near, 0.0); }
         else { lo = fmax(near, 0.0); hi = far; }
         if (!(hi > lo)) { *origin = org; *tau = 0.5 * (lo + hi); return; }                 // b = 0: mu = min/max(D_e, 0)
+        if (bat(e) * bat(e) == 0.0 && shift * sg >= 0.0) {
+            // The nearest pole carries no weight (b_e = 0, or b_e^2 underflows) and lies beyond 0: f is smooth across
+            // it, and a root beyond the pole exists only if f has already changed sign there.  Otherwise the pole
+            // itself is the exterior eigenvalue (the hard case: gradient orthogonal to the softest mode) and the
+            // answer is tau = 0 exactly — the bracket (far, 0) would only halve towards it, 200 sweeps that end a
+            // hair off the pole, where the callers' test for "mu coincides with a pole" no longer sees it.
+            // f at the pole, one step outside it so that the pole's own 0 / 0 term is an honest 0:
+            const Ev ep = eval(shift, sg * fmax(fabs(shift) * 1e-200, 1e-300));
+            if (!(sg * ep.f < 0.0)) { *origin = org; *tau = 0.0; return; }
+        }
         t = far;
         if (t == 0.0) t = 0.5 * (lo + hi);
     } else {

@@ -100,13 +100,18 @@ double rfo_block(int mm, const double* lam, const double* ghat, int o, double al
     double ss = 0.0;
     for (int i = 0; i < mm; ++i) { shat[i] = vh[i] * alpha / den; ss += shat[i] * shat[i]; }
     if (!dshat) return ss;
-    // c = dA/dalpha v : dA = [[2 alpha lam, ghat], [ghat^T, 0]]
+    // c = dA/dalpha v : dA = [[2 alpha lam, ghat], [ghat^T, 0]], wanted on the complement of v only.  A v = mu v reads
+    // alpha^2 lam_i v_i + alpha ghat_i eta = mu v_i (row i) and alpha sum ghat_i v_i = mu eta (last row), hence
+    //     c = (2 mu / alpha) v - (eta ghat, sum ghat_i v_i):
+    // the first term is a multiple of v, which the projection below removes — so it is never formed.  Formed, it
+    // is |2 alpha lam| against a remainder of |ghat| eta: at the scaled-identity Hessian every run starts with
+    // (lam = 70, alpha = 1) the projection then cancelled five digits and ds/dalpha kept seven.
     double last = 0.0;
     for (int i = 0; i < mm; ++i) {
-        c1[i] = 2.0 * alpha * lam[i] * vh[i] + ghat[i] * vh[mm];
+        c1[i] = -ghat[i] * vh[mm];
         last += ghat[i] * vh[i];
     }
-    c1[mm] = last;
+    c1[mm] = -last;
     // x = sum_{j != o} v_j (v_j . c) / (L_j - L_o) = pinv(A - mu) c on the complement of v
     double vc = 0.0;
     for (int i = 0; i <= mm; ++i) vc += vh[i] * c1[i];
