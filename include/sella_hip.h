@@ -543,22 +543,53 @@ int sella_pair_hessian(sella_ctx* ctx, int n, const double* pos, int form, const
 int sella_pair_hvp(sella_ctx* ctx, int n, const double* pos, int form, const double* params, int nshift,
                    const double* shifts, double rcut, const double* V, int k, double* HV);
 
+/* ---- TIP3P water: the potential of tests/integration/test_tip3p_cluster.py (ase/calculators/tip3p.py) ------------- */
+/* Energy and gradient of rigid three-site water (csrc/tip3p.hip: one workgroup per molecule, every molecule pair visited
+ * from both ends, sums reduced in-block — the same bits from call to call).  E = sum over the molecule pairs m < n of
+ * t(d) U_mn, U_mn = 4 epsilon ((sigma/d)^12 - (sigma/d)^6) + k_e sum over the nine site pairs of q_a q_b / r_ab, d the O-O
+ * distance, t = 1 up to rc - width, 1 - y^2 (3 - 2 y) with y = (d - rc + width) / width up to rc, 0 beyond; nothing inside a
+ * molecule.  pos (3 n_mol x 3): consecutive triples, one molecule each, the oxygen at site o: 0 (O H H) or 2 (H H O).
+ * box (3): the edges of an orthorhombic cell, <= 0 for a direction that is not periodic; one shift per molecule pair,
+ * -L rint(D / L) of the O-O difference D, moves all nine site pairs.  params (6): q_H (q_O = -2 q_H), sigma, epsilon, k_e,
+ * rc, width.  A site pair closer than 1e-8 is skipped.  Outputs: *energy, grad (3 n_mol x 3) = dE/dx.  A single molecule is
+ * valid (all zero).  SELLA_E_INVALID (also from sella_calc_tip3p_create) for a null pointer, n_mol <= 0, another o,
+ * positions, box or parameters that are not finite, sigma <= 0, width <= 0 or width > rc, a periodic edge below 2 rc, or
+ * 3 n_mol >= 2^24.                                                                                                    */
+int sella_tip3p_eval(sella_ctx* ctx, int n_mol, const double* pos, int o, const double* box, const double* params,
+                     double* energy, double* grad);
+/* The analytic Hessian d2E/dx2 of the same potential, arguments and limits as for sella_tip3p_eval.
+ *   hessian: out (9 n_mol square, allocated by the caller) is overwritten and stays on the device; exactly symmetric.  The
+ *     switch acts on whole molecule pairs, so the blocks are 9 x 9 per pair of molecules (the diagonal ones included), not
+ *     3 x 3 per pair of atoms; no temporary storage.
+ *   hvp: HV[q] = H V[q] for k vectors, V and HV (k x 9 n_mol) host arrays with one vector per row; no 9 n_mol square
+ *     storage.  The visits of the geometry (a partner inside rc with its nine site pairs' directions and coefficients, the
+ *     switched gradients at the six sites, u_OO and two switch scalars: 548 bytes each) are built once per call and the
+ *     vectors taken through them 16 at a time.
+ * A wrong shape of `out`, k <= 0 or a null pointer: SELLA_E_INVALID.                                                */
+int sella_tip3p_hessian(sella_ctx* ctx, int n_mol, const double* pos, int o, const double* box, const double* params,
+                        sella_mat out);
+int sella_tip3p_hvp(sella_ctx* ctx, int n_mol, const double* pos, int o, const double* box, const double* params,
+                    const double* V, int k, double* HV);
+
 /* ---- calculators that live in the library, and the finite-difference Hessian on top of one ----------------- */
 /* sella/peswrapper.py:413-418 evaluates energy and forces through `atoms.calc`; for a calculator implemented HERE that
  * boundary can be crossed without the host language: sella_calc_eval(calc, x, &f, g) -> energy and gradient dE/dx.
  *   model: f(x) = 1/2 x^T A x + c/3 sum_j (u_j . x)^3, A (n x n resident), U (nu x n host, copied);
  *   emt:   the arguments of sella_emt_eval, fixed at creation (n = 3 natoms);
- *   pair:  the arguments of sella_pair_eval, fixed at creation (n = 3 natoms; parameters and shifts resident).      */
+ *   pair:  the arguments of sella_pair_eval, fixed at creation (n = 3 natoms; parameters and shifts resident);
+ *   tip3p: the arguments of sella_tip3p_eval but the positions, fixed at creation (n = 9 n_mol).                     */
 typedef struct sella_calc sella_calc;
 int sella_calc_model_create(sella_ctx* ctx, sella_mat A, const double* U, int nu, int n, double c, sella_calc** calc);
 int sella_calc_emt_create(sella_ctx* ctx, int natoms, const double* par, int nshift, const double* shifts, double rc,
                           double acut, double cutoff, double beta, sella_calc** calc);
 int sella_calc_pair_create(sella_ctx* ctx, int natoms, int form, const double* params, int nshift, const double* shifts,
                            double rcut, sella_calc** calc);
+int sella_calc_tip3p_create(sella_ctx* ctx, int n_mol, int o, const double* box, const double* params, sella_calc** calc);
 int sella_calc_eval(sella_calc* calc, const double* x, double* energy, double* grad);
 /* Second derivatives at x: the Hessian into out (n x n, allocated by the caller, stays on the device), and its products
  * HV[q] = H V[q] with k host vectors (V, HV: k x n, one vector per row).  emt: sella_emt_hessian / sella_emt_hvp on the
- * calculator's resident constants, bit for bit; pair: sella_pair_hessian / sella_pair_hvp, bit for bit; model:
+ * calculator's resident constants, bit for bit; pair: sella_pair_hessian / sella_pair_hvp, bit for bit; tip3p:
+ * sella_tip3p_hessian / sella_tip3p_hvp, bit for bit; model:
  * A + 2 c sum_j (u_j . x) u_j u_j^T.  Neither counts as a force
  * call (sella_calc_ncalls is unchanged).  Wrong shapes: SELLA_E_INVALID.                                              */
 int sella_calc_hessian(sella_calc* calc, const double* x, sella_mat out);

@@ -117,6 +117,7 @@ SIGNATURES = {
     'sella_calc_emt_create': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double, c_double, c_double,
                                       POINTER(c_void_p)]),
     'sella_calc_pair_create': (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_double, POINTER(c_void_p)]),
+    'sella_calc_tip3p_create': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, POINTER(c_void_p)]),
     'sella_calc_eval': (c_int, [c_void_p, c_void_p, POINTER(c_double), c_void_p]),
     'sella_calc_hessian': (c_int, [c_void_p, c_void_p, c_int]),
     'sella_calc_hvp': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -202,6 +203,9 @@ SIGNATURES = {
                                        c_double, c_double, c_int]),
     'sella_emt_cell_hvp': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_double, c_double,
                                    c_double, c_double, c_void_p, c_int, c_void_p]),
+    'sella_tip3p_eval': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_double_p, c_void_p]),
+    'sella_tip3p_hessian': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int]),
+    'sella_tip3p_hvp': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     'sella_pair_eval': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double_p, c_void_p]),
     'sella_pair_eval_stress': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_double_p,
                                        c_void_p, c_void_p]),

@@ -10,7 +10,8 @@ image; when `ase` imports, its own classes are used instead and these are bypass
               QuadraticCubicModel (SURVEY.md §8d model PES), MorseCluster
               (tests/integration/test_morse_cluster.py), PairLJ — O(N^2) NumPy on the host, the yardsticks of
               Morse and LennardJones, the same pair potentials on the device (csrc/pair.hip) with stress, Hessian,
-              Hessian-vector products and a library form.
+              Hessian-vector products and a library form; TIP3P, rigid three-site water on the device
+              (csrc/tip3p.hip) with Hessian, products and a library form.
 """
 import sys
 import time
@@ -795,6 +796,107 @@ class LennardJones(_DevicePairPotential):
         if not self._params[1] > 0.0:
             raise ValueError('LennardJones: sigma must be positive')
         self.eps, self.sigma = float(eps), float(sigma)
+
+
+# TIP3P (Jorgensen et al., J. Chem. Phys. 79, 926 (1983)) as ase/calculators/tip3p.py states it; the two unit factors
+# from the CODATA 2014 values ase.units uses, named here and nowhere else: 0.1521 kcal/mol in eV, and the Coulomb constant
+# Hartree x Bohr = e^2 / (4 pi eps0) in eV Angstrom
+qH = 0.417
+sigma0 = 3.15061
+epsilon0 = 0.00659568020328023
+_COULOMB = 14.399645351950547
+rOH = 0.9572
+angleHOH = 104.52
+
+
+class TIP3P(Calculator):
+    """Rigid three-site TIP3P water on the device (csrc/tip3p.hip), the model of ASE's `ase.calculators.tip3p.TIP3P`:
+    atoms in consecutive triples, one molecule each, `O H H` or `H H O`; Lennard-Jones (`sigma0`, `epsilon0`) between the
+    oxygens, Coulomb between all sites of different molecules (`qH`, q_O = -2 qH), every molecule pair multiplied by a
+    switch of the O-O distance that falls from 1 at rc - width to 0 at rc.  Nothing acts inside a molecule: the geometry
+    (`rOH`, `angleHOH`) is held by constraints.  Periodic directions need a diagonal cell with edges of at least 2 rc
+    (minimum image, one shift per molecule pair); ValueError otherwise.
+
+    Energy and forces, the analytic Hessian and its products (`get_hessian`, `get_device_hessian`,
+    `hessian_vector_product`), and the library form (`device_calculator()`: whole searches, cohorts, the finite-difference
+    and the exact Hessian-vector operators).  No virial: `get_stress` raises NotImplementedError, and there are no second
+    derivatives with respect to the cell."""
+
+    def __init__(self, rc=5.0, width=1.0):
+        super().__init__()
+        self.rc, self.width = float(rc), float(width)
+        if not (np.isfinite(self.rc) and np.isfinite(self.width) and 0.0 < self.width <= self.rc):
+            raise ValueError('TIP3P: 0 < width <= rc is required')
+        self._params = np.array([qH, sigma0, epsilon0, _COULOMB, self.rc, self.width])
+        self._setup = None
+
+    def _prepare(self, atoms):
+        cell = np.asarray(atoms.cell, dtype=float)
+        pbc = tuple(bool(p) for p in atoms.pbc)
+        key = (tuple(int(z) for z in atoms.numbers), cell.tobytes(), pbc)
+        if self._setup is not None and self._setup[0] == key:
+            return
+        n = len(atoms)
+        if n == 0 or n % 3:
+            raise ValueError(f'TIP3P: {n} atoms are not a whole number of three-site molecules')
+        z = np.asarray(atoms.numbers).reshape(-1, 3)
+        if (z == (8, 1, 1)).all():
+            o = 0
+        elif (z == (1, 1, 8)).all():
+            o = 2
+        else:
+            raise ValueError('TIP3P: the atoms must be consecutive molecules, all O H H or all H H O')
+        box = np.zeros(3)
+        for k in range(3):
+            if not pbc[k]:
+                continue
+            if np.any(np.delete(cell[k], k) != 0.0) or np.any(np.delete(cell[:, k], k) != 0.0) or not cell[k, k] > 0.0:
+                raise ValueError('TIP3P: the cell must be diagonal in its periodic directions (orthorhombic box)')
+            if cell[k, k] < 2.0 * self.rc:
+                raise ValueError(f'TIP3P: the periodic edge {cell[k, k]:.3f} is shorter than 2 rc = {2.0 * self.rc:.3f} '
+                                 f'(minimum image only)')
+            box[k] = cell[k, k]
+        self._setup = (key, dict(nmol=n // 3, o=o, box=box))
+        self._key = None                           # results cached for the old cell are stale
+        self._drop_hessian()
+
+    def _get(self, atoms, stress=False):
+        self._prepare(atoms)
+        return super()._get(atoms, stress)
+
+    def _tip3p_args(self, pos):
+        if self._setup is None:
+            raise RuntimeError('TIP3P: no atoms seen yet (evaluate through an Atoms object first)')
+        S = self._setup[1]
+        return pos, S['o'], S['box'], self._params
+
+    def energy_and_gradient(self, pos):
+        from .device import get_context
+        return get_context().tip3p_eval(*self._tip3p_args(pos))
+
+    def device_hessian(self, pos):
+        """The analytic Hessian (csrc/tip3p.hip: 9 x 9 blocks per pair of molecules, the switch terms included)."""
+        from .device import get_context
+        return get_context().tip3p_hessian(*self._tip3p_args(pos))
+
+    def hessian_products(self, pos, V):
+        from .device import get_context
+        return get_context().tip3p_hvp(*self._tip3p_args(pos), V)
+
+    library_form = True
+
+    def device_calculator(self):
+        """This potential, for the molecules and cell it was last set up for, as a calculator inside the library
+        (`sella_calc_tip3p_create`); None before the first evaluation."""
+        if self._setup is None:
+            return None
+        hit = getattr(self, '_devcalc', None)
+        if hit is None or hit[0] is not self._setup:
+            from .device import DeviceCalculator, get_context
+            S = self._setup[1]
+            hit = (self._setup, DeviceCalculator.tip3p(get_context(), S['nmol'], S['o'], S['box'], self._params))
+            self._devcalc = hit
+        return hit[1]
 
 
 class PairLJ(Calculator):

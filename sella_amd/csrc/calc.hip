@@ -7,9 +7,10 @@
 //   sella_calc_model_*   f(x) = 1/2 x^T A x + c/3 sum_j (u_j . x)^3, A resident (the model PES of SURVEY.md section 8d)
 //   sella_calc_emt_*     effective-medium theory (emt.hip, sella_emt_eval)
 //   sella_calc_pair_*    a Morse or Lennard-Jones pair potential (pair.hip, sella_pair_eval)
+//   sella_calc_tip3p_*   TIP3P water (tip3p.hip, sella_tip3p_eval)
 //   sella_fd_*           H v ~ (g(x0 + eta v^) - g0) / eta (or the central form), seen through a selection of free
 //                        coordinates; every product is remembered as a secant pair for the Hessian update afterwards
-//   sella_hvp_*          H v in closed form (EMT: emt_hessian.hip; pair: pair.hip; model: A v + sum_j 2 c (u_j . x0)(u_j . v) u_j) through the
+//   sella_hvp_*          H v in closed form (EMT: emt_hessian.hip; pair: pair.hip; TIP3P: tip3p.hip; model: A v + sum_j 2 c (u_j . x0)(u_j . v) u_j) through the
 //                        same selection, on a state built once at x0 and owned by the operator: device vector in, device
 //                        vector out, no host wait per product (the third operator kind of sella_davidson, davidson.hip);
 //                        the pairs are recorded on the device.  Not force calls.  The same for the rows of a device panel
@@ -18,6 +19,7 @@
 //                        coordinates [x; p] of a cell run, through the same entries
 #include "emt.h"
 #include "pair.h"
+#include "tip3p.h"
 
 #include <algorithm>
 #include <cmath>
@@ -27,7 +29,7 @@ using namespace sella;
 
 struct sella_calc {
     sella_ctx* c = nullptr;
-    int kind = 0;                     // 0 model, 1 EMT, 2 pair potential
+    int kind = 0;                     // 0 model, 1 EMT, 2 pair potential, 3 TIP3P water
     int n = 0;
     long ncalls = 0;
     // model
@@ -46,6 +48,8 @@ struct sella_calc {
     double* dconst = nullptr;         // EMT: parameter table + shift vectors, resident; model: the rows u_j (nu x ld);
                                       // pair: the parameters as given (3 doubles) + shift vectors
     size_t dconst_bytes = 0;
+    // TIP3P (natoms = 3 molecules' sites; nothing resident: the parameters travel in the kernel arguments)
+    TipPot tip = {};
 };
 
 namespace {
@@ -216,6 +220,14 @@ int sella::calc_queue(sella_calc* k, const double* x, double** g_dev, double** a
         *naux = k->natoms;
         return SELLA_OK;
     }
+    if (k->kind == 3) {
+        double *dem, *dgr;
+        SCHK(tip3p_queue(c, k->tip, x, &dem, &dgr));
+        *g_dev = dgr;
+        *aux_dev = dem;
+        *naux = k->tip.nmol;
+        return SELLA_OK;
+    }
     const int n = k->n, ld = round_up(n, 8), nu = k->nu;
     Mat* A = mat_get(c, k->A);
     if (!A) return SELLA_E_INVALID;
@@ -235,9 +247,10 @@ int sella::calc_queue(sella_calc* k, const double* x, double** g_dev, double** a
 }
 
 double sella::calc_finish(sella_calc* k, const double* x, const double* aux) {
-    if (k->kind == 1 || k->kind == 2) {
+    if (k->kind == 1 || k->kind == 2 || k->kind == 3) {
+        const int ne = k->kind == 3 ? k->tip.nmol : k->natoms;      // per-atom or per-molecule energies, in index order
         double e = 0.0;
-        for (int i = 0; i < k->natoms; ++i) e += aux[i];
+        for (int i = 0; i < ne; ++i) e += aux[i];
         return e;
     }
     const int n = k->n, ld = round_up(n, 8);
@@ -301,6 +314,25 @@ extern "C" int sella_calc_pair_create(sella_ctx* c, int natoms, int form, const 
     return SELLA_OK;
 }
 
+// TIP3P water (tip3p.hip): n_mol molecules as consecutive triples with the oxygen at site o, box edges (<= 0: not periodic),
+// params q_H, sigma, epsilon, k_e, rc, width.  Everything travels in the kernel arguments: nothing is resident.
+extern "C" int sella_calc_tip3p_create(sella_ctx* c, int n_mol, int o, const double* box, const double* params, sella_calc** out) {
+    TipPot pot;
+    const double origin[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    // (the positions come with every call: one molecule's worth of zeros stands in for them in the check)
+    const char* bad = (!c || !out || n_mol <= 0) ? "invalid arguments" : tip3p_pot_make(1, origin, o, box, params, &pot);
+    if (!bad && (long)3 * n_mol >= (1L << 24)) bad = "at most 2^24 sites";
+    if (bad) {
+        set_error("calc_tip3p: %s", bad);
+        return SELLA_E_INVALID;
+    }
+    pot.nmol = n_mol;
+    sella_calc* k = new sella_calc();
+    k->c = c; k->kind = 3; k->n = 9 * n_mol; k->natoms = 3 * n_mol; k->tip = pot;
+    *out = k;
+    return SELLA_OK;
+}
+
 // energy and gradient dE/dx at x (n entries)
 extern "C" int sella_calc_eval(sella_calc* k, const double* x, double* f, double* g) {
     if (!k || !x || !f || !g) return SELLA_E_INVALID;
@@ -331,6 +363,7 @@ extern "C" int sella_calc_hessian(sella_calc* k, const double* x, sella_mat out)
     if (k->kind == 2)
         return pair_hessian_resident(c, k->natoms, x, k->form, k->pot, k->nshift, k->shifts.data(),
                                      k->dconst ? k->dconst + 3 : nullptr, out);
+    if (k->kind == 3) return tip3p_hessian_resident(c, k->tip, x, out);
     const int n = k->n, nu = k->nu, ld = round_up(n, 8);
     Mat *A = mat_get(c, k->A), *H = mat_get(c, out);
     if (!A) {
@@ -371,6 +404,7 @@ extern "C" int sella_calc_hvp(sella_calc* k, const double* x, const double* V, i
                                 k->cutoff, k->beta, V, nv, HV);
     if (k->kind == 2)
         return pair_hvp_resident(c, k->natoms, x, k->form, k->pot, k->nshift, k->shifts.data(), V, nv, HV);
+    if (k->kind == 3) return tip3p_hvp_resident(c, k->tip, x, V, nv, HV);
     const int n = k->n, nu = k->nu, ld = round_up(n, 8);
     Mat* A = mat_get(c, k->A);
     if (!A) {
@@ -531,6 +565,7 @@ struct sella_hvp {
     bool select = false;
     EmtHvpState emt;                      // EMT kind
     PairHvpState pair;                    // pair kind
+    TipHvpState tip;                      // TIP3P kind
     // the kind of positions and cell (sella_hvp_create_cell): n = nx + mc and m = mx + mc, the mc cell parameters behind the
     // nx position coordinates (mx of them free: inv covers the positions); nb counts the workgroups of the positions
     bool cell = false;
@@ -558,6 +593,7 @@ static void hvp_release(sella_hvp* o) {
     if (o->cell) emt_hvp_state_destroy(c, &o->cemt.s);
     else if (o->calc->kind == 1) emt_hvp_state_destroy(c, &o->emt);
     else if (o->calc->kind == 2) pair_hvp_state_destroy(c, &o->pair);
+    else if (o->calc->kind == 3) tip3p_hvp_state_destroy(c, &o->tip);
     for (double* p : o->chunks) dev_free(c, p, o->chunk_bytes);
     if (o->aux) dev_free(c, o->aux, o->aux_bytes);
     if (o->blk) dev_free(c, o->blk, o->blk_bytes);
@@ -619,6 +655,8 @@ extern "C" int sella_hvp_create(sella_calc* calc, int n, const double* x0, const
                                   calc->acut, calc->cutoff, calc->beta, &o->emt);
     } else if (calc->kind == 2) {
         st = pair_hvp_state_create(c, calc->natoms, x0, calc->form, calc->pot, calc->nshift, calc->shifts.data(), &o->pair);
+    } else if (calc->kind == 3) {
+        st = tip3p_hvp_state_create(c, calc->tip, x0, &o->tip);
     } else {
         if (nu > 0) {
             std::vector<double> S((size_t)nu * ld, 0.0);               // rows 2 c (u_j . x0) u_j, as sella_calc_hessian builds them
@@ -648,7 +686,7 @@ extern "C" int sella_hvp_create_cell(sella_calc* calc, int n, const double* x0, 
         return SELLA_E_INVALID;
     }
     if (calc->kind != 1) {
-        static const char* const names[] = {"model", "EMT", "pair-potential"};
+        static const char* const names[] = {"model", "EMT", "pair-potential", "TIP3P"};
         set_error("hvp cell operator: only the EMT calculator has second derivatives with respect to the cell, not the %s "
                   "calculator (kind %d)", names[calc->kind], calc->kind);
         return SELLA_E_INVALID;
@@ -702,6 +740,7 @@ int sella::hvp_device_apply(sella_hvp* o, const double* x, double* y) {
     SELLA_LAUNCHB(c, hvp_scatter_kernel, hvp_scatter_vb, 256, dim3(o->nb), dim3(256), 0, n, x, (const int*)o->inv, v, o->part);
     if (k->kind == 1) return emt_hvp_state_apply(c, o->emt, v, hv, o->part, o->nb, o->inv, y, flag);
     if (k->kind == 2) return pair_hvp_state_apply(c, o->pair, v, hv, o->part, o->nb, o->inv, y, flag);
+    if (k->kind == 3) return tip3p_hvp_state_apply(c, o->tip, v, hv, o->part, o->nb, o->inv, y, flag);
     Mat* A = mat_get(c, k->A);
     if (!A) {
         set_error("hvp operator: the model calculator's matrix A is gone");
@@ -778,6 +817,7 @@ int sella::hvp_device_apply_block(sella_hvp* o, const double* X, int ldx, int nh
     }
     if (k->kind == 1) return emt_hvp_state_apply_block(c, o->emt, V, ldv, nh, o->inv, Y, ldy);
     if (k->kind == 2) return pair_hvp_state_apply_block(c, o->pair, V, ldv, nh, o->inv, Y, ldy);
+    if (k->kind == 3) return tip3p_hvp_state_apply_block(c, o->tip, V, ldv, nh, o->inv, Y, ldy);
     SCHK(launch_panel16(c, A->d, n, n, A->ld, V, nh, o->bhv, o->ld));
     if (k->nu > 0) SCHK(launch_panel16(c, k->dconst, k->nu, n, o->ld, V, nh, o->bt, o->ldt));
     SELLA_LAUNCHB(c, hvp_model_finish_block_kernel, hvp_model_finish_block_vb, 256, dim3(o->nb, nh), dim3(256), 0, n, k->nu, o->ld,
@@ -839,6 +879,8 @@ extern "C" int sella_hvp_diag(sella_hvp* o, double* diag) {
         SCHK(emt_hvp_state_diag(c, o->emt, o->inv, o->dy));
     } else if (k->kind == 2) {
         SCHK(pair_hvp_state_diag(c, o->pair, o->inv, o->dy));
+    } else if (k->kind == 3) {
+        SCHK(tip3p_hvp_state_diag(c, o->tip, o->inv, o->dy));
     } else {
         Mat* A = mat_get(c, k->A);
         if (!A) {

@@ -760,6 +760,39 @@ class Context:
                                         ptr(V), V.shape[0], ptr(HV)))
         return HV.reshape(shape)
 
+    # ---- TIP3P water ------------------------------------------------------------------------------------
+    def tip3p_eval(self, pos, o, box, params):
+        """(energy, gradient (3 n_mol, 3)) of TIP3P water (`sella_tip3p_eval`): pos (3 n_mol, 3) in consecutive triples with
+        the oxygen at site o (0 or 2), box (3,) the edges of the orthorhombic cell (<= 0: not periodic), params
+        (q_H, sigma, epsilon, k_e, rc, width)."""
+        pos, o, box, params = _tip3p_args(pos, o, box, params)
+        e = c_double(0.0)
+        grad = np.empty_like(pos)
+        check(_lib.lib().sella_tip3p_eval(self._h, pos.shape[0] // 3, ptr(pos), o, ptr(box), ptr(params), byref(e), ptr(grad)))
+        return e.value, grad
+
+    def tip3p_hessian(self, pos, o, box, params):
+        """The analytic Cartesian Hessian of TIP3P water as a (9 n_mol square) `DeviceMatrix` (`sella_tip3p_hessian`):
+        exactly symmetric, left on the device."""
+        pos, o, box, params = _tip3p_args(pos, o, box, params)
+        out = self.zeros(pos.size, pos.size)
+        try:
+            check(_lib.lib().sella_tip3p_hessian(self._h, pos.shape[0] // 3, ptr(pos), o, ptr(box), ptr(params), out.handle))
+        except Exception:
+            out.free()
+            raise
+        return out
+
+    def tip3p_hvp(self, pos, o, box, params, V):
+        """H V[q] for the rows of V (k, 9 n_mol) (or one vector (9 n_mol,)) without forming H (`sella_tip3p_hvp`); same
+        shape as V."""
+        pos, o, box, params = _tip3p_args(pos, o, box, params)
+        V, shape = _hvp_vectors(V, pos.size)
+        HV = np.empty_like(V)
+        check(_lib.lib().sella_tip3p_hvp(self._h, pos.shape[0] // 3, ptr(pos), o, ptr(box), ptr(params), ptr(V), V.shape[0],
+                                         ptr(HV)))
+        return HV.reshape(shape)
+
     # ---- profiling ---------------------------------------------------------------------------
     def prof_enable(self, on=True):
         check(_lib.lib().sella_prof_enable(self._h, int(bool(on))))
@@ -803,6 +836,15 @@ def _pair_args(pos, form, params, shifts, rcut):
     return pos, number, params, shifts, 0.0 if rcut is None else float(rcut)
 
 
+def _tip3p_args(pos, o, box, params):
+    """The arguments of the `sella_tip3p_*` entries as the library takes them: positions (3 n_mol, 3), the oxygen's site,
+    the box edges (3,) and the six parameters.  Wrong shapes raise ValueError."""
+    pos = as_f64(pos)
+    if pos.ndim != 2 or pos.shape[1] != 3 or pos.shape[0] == 0 or pos.shape[0] % 3:
+        raise ValueError(f'expected positions of shape (3 n_mol, 3), got {pos.shape}')
+    return pos, int(o), as_f64(box, (3,)), as_f64(params, (6,))
+
+
 class DeviceCalculator:
     """A calculator that lives in the library (`sella_calc_*`, csrc/calc.hip): energy and gradient without a
     host-language frame, so that the finite-difference products of an iterative diagonalisation are library calls."""
@@ -833,6 +875,14 @@ class DeviceCalculator:
         h = c_void_p()
         check(_lib.lib().sella_calc_pair_create(ctx._h, int(natoms), number, ptr(params), shifts.shape[0], ptr(shifts), rcut,
                                                 byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def tip3p(cls, ctx, n_mol, o, box, params):
+        """TIP3P water (`sella_calc_tip3p_create`): arguments as for `Context.tip3p_eval`, without the positions."""
+        _, o, box, params = _tip3p_args(np.zeros((3 * int(n_mol), 3)), o, box, params)
+        h = c_void_p()
+        check(_lib.lib().sella_calc_tip3p_create(ctx._h, int(n_mol), o, ptr(box), ptr(params), byref(h)))
         return cls(ctx, h)
 
     def eval(self, x):
